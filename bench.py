@@ -3,6 +3,7 @@
 ML-KEM-768 encaps+decaps pairs per second at batch 2^20 (BASELINE configs[2]), inputs resident in HBM.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload kem768|kem1024|kem512|ntt] [--rehearse] [--inproc]
+                 [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch: Encaps_internal over 2^20 (ek, m) followed by KEM_Decaps
 (hash check included, as the reference's public API does) over the 2^20 (dk, c) it produced.  Keys come from the
@@ -18,6 +19,9 @@ barrier and its own synchronize, shader clock and socket power sampled on that r
 the aggregate; `correct` is the AND over all ranks and every rank exits non-zero when it is false.
 --inproc: the same workload in ONE process through mlkem_{encaps,decaps}_multi_dev, one member per visible device (members
 repeat devices when there are fewer devices than --gpus: a rehearsal, labelled as such) -- the in-process form of the shard.
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned to its caller as DIR/<name>.npy
+(float32; the item indices in float64) for a fixed, seeded sample of the batch's items (at most 64 MB in all), so that two
+builds run with the same arguments can be compared output for output.
 
 At N = 1 the line also carries `also`: BASELINE configs[1] (NTT-only), configs[3] (ML-KEM-1024 KeyGen+Encaps+Decaps), small_calls (1 / 64 / 768-item call pairs)
 measured in the same process right after the headline, each with value / ms_per_step / correct / roofline.
@@ -55,6 +59,8 @@ ALGO_BYTES = {"kem768": 5856, "kem1024": 12768, "kem512": 6560, "ntt": 2048,
 # 32-bit VALU lane-operations per unit, from the ISA of this build
 KECCAK_PERM_LANE_OPS = 24 * 180
 TIMING_PASSES = 3   # passes of the per-kernel HIP-event timing leg
+DUMP_BYTES = 64_000_000   # --dump-outputs: budget of all files together, .npy headers included
+DUMP_SEED = 0xD0
 
 
 def kernel_label(kernel_name):
@@ -179,6 +185,20 @@ def gather_per_gpu(entry):
     out = [None] * dist.get_world_size()
     dist.all_gather_object(out, entry)
     return out
+
+
+def dump_outputs(out_dir, n, arrays):
+    """--dump-outputs: `arrays` maps a name to a device tensor whose first dimension is the item.  Rows of a fixed seeded
+    sample of the n items (all of them when they fit DUMP_BYTES as float32) go to out_dir/<name>.npy in float32, their
+    indices to out_dir/item_index.npy in float64."""
+    per_item = 8 + sum(4 * (t[0].numel() if t.dim() > 1 else 1) for t in arrays.values())
+    rows = min(n, (DUMP_BYTES - 256 * (len(arrays) + 1)) // per_item)
+    idx = np.arange(n) if rows == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, rows, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "item_index.npy"), idx.astype(np.float64))
+    for name, t in arrays.items():
+        sel = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), sel.to(torch.float32).cpu().numpy())
 
 
 def host_cores():
@@ -414,6 +434,10 @@ def run_kem(args, pset, rank, world, device):
     own = time.perf_counter() - t0      # this rank's own time: per_gpu
     barrier(world)
     elapsed = max_over_ranks(time.perf_counter() - t0, world, device)
+    if args.dump_outputs and rank == 0:   # what the last timed step handed its caller
+        outs = {"ek": ek, "dk": dk} if timed_keygen else {}
+        outs.update({"c": c, "K_encaps": K, "K_decaps": K2, "status": st})
+        dump_outputs(args.dump_outputs, n, outs)
 
     # shader clock and socket power on EVERY rank, right behind the timed region while all ranks keep stepping together
     clock_power = clock_power_probe(step, device)
@@ -554,6 +578,8 @@ def run_ntt(args, rank, world, device):
     own = time.perf_counter() - t0
     barrier(world)
     elapsed = max_over_ranks(time.perf_counter() - t0, world, device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, n, {"ntt": fh, "intt": f2})
     clock_power = clock_power_probe(step, device)
     barrier(world)
     ok = bool(torch.equal(f, f2)) and int(fh.min()) >= 0 and int(fh.max()) < 3329
@@ -793,13 +819,27 @@ def small_calls(device):
     return out
 
 
+def positive_int(text):
+    v = int(text)
+    if v < 1:
+        raise argparse.ArgumentTypeError("must be at least 1")
+    return v
+
+
+def nonnegative_int(text):
+    v = int(text)
+    if v < 0:
+        raise argparse.ArgumentTypeError("must not be negative")
+    return v
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=None,
+    ap.add_argument("--steps", type=positive_int, default=None,
                     help="timed steps (default 20: ~0.4 s, long enough for the power-capped clock to settle; 200 for the "
                          "sub-millisecond NTT workload)")
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--warmup", type=nonnegative_int, default=3)
     ap.add_argument("--workload", default="kem768", choices=("kem768", "kem1024", "kem512", "ntt", "kem768_shared"))
     ap.add_argument("--batch", type=int, default=1 << 20, help="items per GPU per step (BASELINE: 2^20)")
     ap.add_argument("--chunk", type=int, default=0, help="engine chunk size in items (0 = library default)")
@@ -810,12 +850,16 @@ def main():
                          "has fewer GPUs than ranks)")
     ap.add_argument("--inproc", action="store_true",
                     help="one process, --gpus members through mlkem_*_multi_dev (member r on device r %% visible devices)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last one (a fixed sample of items) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 200 if args.workload == "ntt" else 20
     args.cpu_budget = (14.0, 8.0, 4.0)   # CPU-seconds of work for the reference -O2 / reference -O0 / port legs
 
     if args.inproc:
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs covers the one-process-per-GPU path, not --inproc")
         return main_inproc(args)
     rank, world, local = dist_setup(args.gpus, args.rehearse)
     if not torch.cuda.is_available():
@@ -833,7 +877,7 @@ def main():
         # `value` above is configs[2]); same timing discipline, their own step counts, their own CPU legs
         for wl2, steps2 in (("ntt", 200), ("kem1024", 10)):
             a2 = argparse.Namespace(**vars(args))
-            a2.workload, a2.steps, a2.warmup = wl2, steps2, 2
+            a2.workload, a2.steps, a2.warmup, a2.dump_outputs = wl2, steps2, 2, None
             a2.cpu_budget = (8.0, 0.0, 2.0)   # configs[3]: reference -O2 and port legs (the -O0 leg is on the headline)
             el2, ok2, ex2 = run_workload(wl2, a2, rank, world, device)
             e2 = entry(wl2, a2, el2, ok2, ex2, world)

@@ -50,14 +50,28 @@ def oracle():
 
 
 @pytest.fixture(scope="session")
-def ref():
-    """The real reference build (oracle/_ref).  Present in the build container and, as a prebuilt
-    .so, on the GPU box; tests that need it skip when it is absent."""
-    from oracle.loader import Ref
-    try:
-        return Ref()
-    except (FileNotFoundError, RuntimeError, OSError) as e:  # pragma: no cover
-        pytest.skip(f"reference build unavailable: {e}")
+def _ref_store():
+    """Answers of the live reference collected under MLKEM_REF_RECORD=1; written to tests/golden/ref_calls.npz at the end."""
+    from oracle import ref_replay
+    store = {}
+    yield store
+    if ref_replay.RECORD and store:
+        ref_replay.save(store)
+
+
+@pytest.fixture(scope="session")
+def ref(_ref_store):
+    """The real reference build (oracle/_ref, -O2) when it exists, otherwise its recorded answers
+    (tests/golden/ref_calls.npz, oracle/ref_replay.py)."""
+    from oracle.ref_replay import open_ref
+    return open_ref(o0=False, store=_ref_store)
+
+
+@pytest.fixture(scope="session")
+def ref_o0(_ref_store):
+    """The reference built at its makefile's own flags (-O0), live or recorded like `ref`."""
+    from oracle.ref_replay import open_ref
+    return open_ref(o0=True, store=_ref_store)
 
 
 def unhex(s):

@@ -354,6 +354,29 @@ def test_bench_inproc_members_line(tmp_path):
     assert abs(j["value"] - 3 * 8192 * 2 / (j["ms_per_step"] * 2e-3)) / j["value"] < 1e-6
 
 
+def test_bench_dump_outputs_are_the_last_steps_results(tmp_path, oracle):
+    """--dump-outputs: two runs with the same arguments write the same arrays, and they are what the oracle computes for the
+    bench's documented inputs (at batch 4096 every seed is the SHAKE128 expander's); --steps sets the timed steps."""
+    dumps = []
+    for run in range(2):
+        out = tmp_path / ("run%d" % run)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "4096",
+                            "--no-also", "--no-cpu", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+        j = _one_json_line(r)
+        assert j["steps"] == 3 and j["correct"] is True
+        dumps.append({f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))})
+    a, b = dumps
+    assert sorted(a) == ["K_decaps", "K_encaps", "c", "item_index", "status"]
+    assert all(a[k].dtype == (np.float64 if k == "item_index" else np.float32) and (a[k] == b[k]).all() for k in a)
+    assert (a["item_index"] == np.arange(4096)).all() and sum(v.nbytes for v in a.values()) <= 64_000_000
+    d, z, m = (seeds("mlkem-bench-" + x, 4096, 0xC0FFEE) for x in "dzm")
+    ek, _ = oracle.keygen(768, d, z)
+    c, K = oracle.encaps(768, ek, m)
+    assert (a["c"] == c).all() and (a["K_encaps"] == K).all() and (a["K_decaps"] == K).all() and (a["status"] == 0).all()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
 def test_bench_default_line_has_three_cpu_legs(tmp_path):
     """the N = 1 line: cpu_baseline carries reference -O2, reference -O0 (the reference makefile's flags) and the port, each
     with its core count and a byte comparison against the GPU; the roofline is the dominant kernel's by the algorithmic-bytes

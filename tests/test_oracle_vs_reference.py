@@ -1,5 +1,6 @@
-"""CPU tier: the oracle against the LIVE reference build (oracle/_ref/libmlkem_ref.so), on fresh
-random inputs each run is NOT wanted — inputs are seeded.  Skips when the reference build is absent.
+"""CPU tier: the oracle against the reference build (oracle/_ref/libmlkem_ref.so), on seeded inputs.  Where that build is
+absent (a clean checkout carries no reference sources) the reference's answers come from tests/golden/ref_calls.npz, which
+recorded these very calls (oracle/ref_replay.py).
 Also covers BASELINE config[0]: ML-KEM-512 single KeyGen+Encaps+Decaps on the CPU via ml_kem.c."""
 import numpy as np
 import pytest
@@ -98,16 +99,13 @@ def test_sha3_b_appends_the_callers_suffix_verbatim(ref, oracle, golden):
         assert (oracle.sponge_bits_sfx(g["rate_bytes"], sfx[:nsfx], bits, want.size) == want).all(), g["sfx"]
 
 
-def test_inverse_ntt_above_q_is_undefined_in_the_reference(oracle):
+def test_inverse_ntt_above_q_is_undefined_in_the_reference(ref, ref_o0, oracle):
     """Why mlkem_intt's contract is [0, q): for inputs >= q the reference's InverseNTT (ml_kem.c:364-367) computes
     Q - (t - f[j+len]) in a 24-bit field and multiplies it by zeta in a (promoted, signed) int, which overflows: the
     reference built with its own makefile flags (-O0) and the -O2 build return DIFFERENT polynomials.  There is nothing
     to be bit-exact against; the forward NTT has no such overflow and both builds (and the oracle) agree on every
     12-bit input, including those whose outputs stay >= q."""
-    from oracle.loader import Ref
-    if not (Ref.available() and Ref.available(o0=True)):
-        pytest.skip("reference builds unavailable")
-    r2, r0 = Ref(), Ref(o0=True)
+    r2, r0 = ref, ref_o0
     rng = np.random.default_rng(1)
     differ = 0
     for _ in range(20):
