@@ -42,6 +42,7 @@ ABI_SYMBOLS = (
     "mlkem_keygen_multi", "mlkem_encaps_multi", "mlkem_decaps_multi",
     "mlkem_keygen_multi_dev", "mlkem_encaps_multi_dev", "mlkem_decaps_multi_dev", "mlkem_multi_sync", "mlkem_multi_stream", "mlkem_stream_last_staged",
     "mlkem_vector_multiply_dev", "mlkem_poly_add_dev", "mlkem_poly_sub_dev",
+    "mlkem_decaps_seed_dev", "mlkem_decaps_seed",
 )
 SHIM_SYMBOLS = ("init", "KEM_KeyGen", "KEM_Encaps", "KEM_Decaps", "ml_errno", "sha3_b", "sha3_h", "sha3_s", "h2b", "b2h",
                 "SampleNTT", "SamplePolyCBD", "NTT", "InverseNTT")
@@ -80,6 +81,8 @@ def load_library():
     L.mlkem_keygen_dev.argtypes = [vp, i32, sz, vp, vp, vp, vp, vp]
     L.mlkem_encaps_dev.argtypes = [vp, i32, sz, vp, vp, vp, vp, vp]
     L.mlkem_decaps_dev.argtypes = [vp, i32, sz, vp, vp, vp, vp, vp]
+    L.mlkem_decaps_seed_dev.argtypes = [vp, i32, sz, vp, vp, vp, vp]
+    L.mlkem_decaps_seed.argtypes = [i32, sz, vp, vp, vp]
     L.mlkem_encaps_status_dev.argtypes = [vp, i32, sz, vp, vp, vp, vp, vp, vp]
     L.mlkem_ctx_set_conformance.argtypes = [vp, i32]
     L.mlkem_ctx_debug_stages.argtypes = [vp, C.c_uint]
@@ -294,6 +297,19 @@ class MLKEM:
         self._check(self.lib.mlkem_decaps_dev(self._ctx, self.param_set, n, dk.data_ptr(), c.data_ptr(), K.data_ptr(), sp,
                                               self._stream()))
         return K, (status if hash_check else None)
+
+    def decaps_seed(self, seed, c, K=None):
+        """Decapsulation from 64-byte seed-format keys (FIPS 203 §3.3): seed [n,64] = d || z, c [n,c_len] -> K [n,32]
+        = Decaps_internal(KeyGen_internal(d, z).dk, c), without the expanded dk ever reaching memory the caller sees."""
+        torch = self.torch
+        seed, c = self._dev(seed, torch.uint8, 64), self._dev(c, torch.uint8, self.c_len)
+        n = c.shape[0]
+        if seed.shape[0] != n:
+            raise MLKEMError(-101, "seed and c batch sizes differ")
+        K = self._out(n, 32, given=K)
+        self._check(self.lib.mlkem_decaps_seed_dev(self._ctx, self.param_set, n, seed.data_ptr(), c.data_ptr(), K.data_ptr(),
+                                                   self._stream()))
+        return K
 
     # reference-style aliases
     KeyGen_internal = keygen

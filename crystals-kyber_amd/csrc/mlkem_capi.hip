@@ -65,6 +65,11 @@ struct mlkem_ctx {
     // to its own context instead (stream_op).
     bool side_allowed = true;
     hipStream_t own_side = nullptr;
+    // staging of seed-format Decaps calls above small_max (decaps_seed_run: d, z, ek, dk per item), chunk_items items of ML-KEM-1024
+    // (4800 bytes each).  Allocated with the first such call, not with the context: the scratch every context carries does not grow for a call type most never make.  Zeroed after
+    // every call and before it is freed.
+    uint8_t* seed_stage = nullptr;
+    size_t seed_stage_bytes = 0;
 };
 
 // called by the *_dev entry points that fork: gives the context its side stream the first time a call fits one chunk
@@ -212,6 +217,10 @@ void mlkem_ctx_destroy(mlkem_ctx* ctx) {
     }
     if (ctx->ws.ev_fork) (void)hipEventDestroy(ctx->ws.ev_fork);
     if (ctx->ws.ev_join) (void)hipEventDestroy(ctx->ws.ev_join);
+    if (ctx->seed_stage) {
+        (void)hipMemset(ctx->seed_stage, 0, ctx->seed_stage_bytes);   // d, z and the expanded dk of the last chunk
+        (void)hipFree(ctx->seed_stage);
+    }
     if (ctx->scratch) {
         (void)hipMemset(ctx->scratch, 0, ctx->scratch_bytes);   // r, m', K', K-bar, PRF output: secret-dependent intermediates
         (void)hipFree(ctx->scratch);
@@ -364,6 +373,36 @@ int mlkem_decaps_dev(mlkem_ctx* ctx, int set, size_t n, const uint8_t* dk, const
     hipStream_t st = static_cast<hipStream_t>(stream);
     ctx_arm_side(ctx, n);
     decaps_dispatch(st, set, n, dk, c, K, status, status != nullptr, ctx->ws);
+    HIP_TRY(hipGetLastError());
+    return MLKEM_OK;
+}
+
+int mlkem_decaps_seed_dev(mlkem_ctx* ctx, int set, size_t n, const uint8_t* seed, const uint8_t* c, uint8_t* K, void* stream) {
+    ParamSet p;
+    if (!param_set(set, p)) return MLKEM_ERR_PARAM_SET;
+    if (!ctx_ok(ctx) || (n && (!seed || !c || !K))) return MLKEM_ERR_ARG;
+    if (!aligned16(seed) || !aligned16(c) || !aligned16(K)) return MLKEM_ERR_ARG;
+    if (n == 0) return MLKEM_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n <= ctx->ws.small_max(p.k)) {   // one launch; nothing of the expanded key leaves LDS
+        decaps_seed_dispatch(st, set, n, seed, c, K, nullptr, 0, ctx->ws);
+        HIP_TRY(hipGetLastError());
+        return MLKEM_OK;
+    }
+    if (!ctx->seed_stage) {   // once, for a whole chunk of the largest parameter set: no later call reallocates (or synchronises)
+        ParamSet p4;
+        (void)param_set(1024, p4);
+        const size_t bytes = ctx->ws.cap * seed_stage_bytes(p4);
+        if (!hip_ok(hipMalloc(&ctx->seed_stage, bytes), "hipMalloc(seed staging)")) {
+            ctx->seed_stage = nullptr;
+            return MLKEM_ERR_ALLOC;
+        }
+        ctx->seed_stage_bytes = bytes;
+    }
+    const size_t stage_items = std::min(n, ctx->ws.cap), used = stage_items * seed_stage_bytes(p);
+    ctx_arm_side(ctx, stage_items);
+    decaps_seed_dispatch(st, set, n, seed, c, K, ctx->seed_stage, stage_items, ctx->ws);
+    HIP_TRY(hipMemsetAsync(ctx->seed_stage, 0, used, st));   // after the call's last reader, in stream order
     HIP_TRY(hipGetLastError());
     return MLKEM_OK;
 }
@@ -964,7 +1003,13 @@ int guarded(Fn fn) {
 int kem_stream(StreamEngine& e, int op, int set, size_t n, const void* a, const void* b, void* x, void* y, size_t chunk, bool pre_locked = false) {
     ParamSet p;
     if (!param_set(set, p)) return MLKEM_ERR_PARAM_SET;
-    if (n && (!a || !b || !x || !y)) return MLKEM_ERR_ARG;
+    if (n && (!a || !b || !x || (!y && op != 3))) return MLKEM_ERR_ARG;
+    if (op == 3) {   // decaps from seeds: seed, c -> K
+        std::vector<Span> sp = {{a, nullptr, 64}, {b, nullptr, p.c_len}, {nullptr, x, 32}};
+        return stream_op(e, n, chunk, sp, [&](mlkem_ctx* ctx, size_t cnt, const std::vector<void*>& v, hipStream_t st) {
+            return mlkem_decaps_seed_dev(ctx, set, cnt, (const uint8_t*)v[0], (const uint8_t*)v[1], (uint8_t*)v[2], st);
+        }, pre_locked);
+    }
     if (op == 0) {   // keygen: d, z -> ek, dk
         std::vector<Span> sp = {{a, nullptr, 32}, {b, nullptr, 32}, {nullptr, x, p.ek_len}, {nullptr, y, p.dk_len}};
         return stream_op(e, n, chunk, sp, [&](mlkem_ctx* ctx, size_t cnt, const std::vector<void*>& v, hipStream_t st) {
@@ -1112,6 +1157,16 @@ int mlkem_decaps(int set, size_t n, const uint8_t* dk, const uint8_t* c, uint8_t
     return guarded([&]() -> int {
         std::vector<int32_t> st(n);   // the caller did not ask for the hash-check codes; K does not depend on them
         return mlkem_decaps_stream(set, n, dk, c, K, st.data(), 0);
+    });
+}
+int mlkem_decaps_seed(int set, size_t n, const uint8_t* seed, const uint8_t* c, uint8_t* K) {
+    ParamSet p;
+    if (!param_set(set, p)) return MLKEM_ERR_PARAM_SET;
+    if (n && (!seed || !c || !K)) return MLKEM_ERR_ARG;
+    return guarded([&]() -> int {   // an engine lane of the current device, like the other host-pointer KEM calls (no combining)
+        HostRef hs = host_state_current();
+        if (!hs) return MLKEM_ERR_NO_DEVICE;
+        return kem_on_free_engine(hs.get(), 3, set, n, seed, c, K, nullptr, 0);
     });
 }
 int mlkem_keygen_stream(int set, size_t n, const uint8_t* d, const uint8_t* z, uint8_t* ek, uint8_t* dk, size_t chunk_items) {

@@ -378,6 +378,16 @@ __global__ void __launch_bounds__(256) k_status_fill(size_t n, const uint8_t* __
     const int32_t v = diff ? -5 : 0;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) status[i] = v;
 }
+// k_seed_split — 64-byte decapsulation-key seeds d || z -> the d and z arrays KeyGen takes (one 16-byte piece per thread)
+__global__ void __launch_bounds__(256) k_seed_split(size_t n, const uint4* __restrict__ seed, uint4* __restrict__ d, uint4* __restrict__ z) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= 4 * n) return;
+    const size_t item = g >> 2;
+    const unsigned part = (unsigned)(g & 3);
+    const uint4 v = seed[g];
+    if (part < 2) d[2 * item + part] = v;
+    else z[2 * item + part - 2] = v;
+}
 
 // ------------------------------------------------------------------------------------------------
 // k_hash_decaps — KEM_Decaps hash check (ml_kem.c:1336-1350) and Decaps_internal's hashing

@@ -639,7 +639,9 @@ encrypt2_body(float2 (*xch)[2][128], size_t item0, size_t n, const uint8_t* __re
 // EXEC masks; for even k the last v row is computed by both halves and stored by the lower one.
 // Pointers address the item itself (no item index); `xch` = K2Lds<(K + 2) / 2 or more>::xch of the wave.
 // ------------------------------------------------------------------------------------------------
-template <int K, int ETA1, int DU, int DV, bool COMPARE>
+// A_T: `A` holds A-hat itself as KeyGen sampled it (entry a * K + b = A-hat[a][b]) and is read transposed; otherwise it holds
+// A-hat^T as Encaps / Decaps sample it
+template <int K, int ETA1, int DU, int DV, bool COMPARE, bool A_T = false>
 __device__ __forceinline__ void
 encrypt1_body(float2 (*xch)[2][128], const uint8_t* __restrict__ ek, const uint8_t* __restrict__ msg, const uint16_t* __restrict__ A,
               const uint8_t* __restrict__ prf, uint8_t* __restrict__ c_out, const uint8_t* __restrict__ c_in, const uint8_t* __restrict__ Kp,
@@ -666,7 +668,7 @@ encrypt1_body(float2 (*xch)[2][128], const uint8_t* __restrict__ ek, const uint8
                 const uint32_t* gp = reinterpret_cast<const uint32_t*>(ek + 384 * b) + 3 * nb;
                 a_all[i][b].x = gp[0]; a_all[i][b].y = gp[1]; a_all[i][b].z = gp[2]; a_all[i][b].w = 0u;
             } else {
-                a_all[i][b] = *reinterpret_cast<const uint4*>(A + (a * K + b) * 256 + 8 * nb);
+                a_all[i][b] = *reinterpret_cast<const uint4*>(A + (A_T ? b * K + a : a * K + b) * 256 + 8 * nb);
             }
         }
         raw_e[i] = k2_cbd_load_nat2(prf + (K + a) * PS, nb);

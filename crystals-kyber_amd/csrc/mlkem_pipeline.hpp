@@ -395,6 +395,37 @@ inline void decaps_run(stream_t st, const ParamSet& p, size_t n, const uint8_t* 
     }
 }
 
+// ---- decapsulation from 64-byte seeds (FIPS 203 §3.3): K = Decaps_internal(KeyGen_internal(d, z).dk, c) --------------------
+// Bytes per item of the staging region the batch path needs: d, z, ek, dk.  `stage` holds room for `stage_items` items; the
+// caller owns it (a context allocates it with its first batch-path seed call and zeroes it after every call).
+inline size_t seed_stage_bytes(const ParamSet& p) { return 64 + (size_t)p.ek_len + (size_t)p.dk_len; }
+template <int K, int ETA1, int DU, int DV>
+inline void decaps_seed_run(stream_t st, const ParamSet& p, size_t n, const uint8_t* seed, const uint8_t* c, uint8_t* Kout, uint8_t* stage,
+                            size_t stage_items, const Workspace& ws) {
+    if (n == 0) return;
+    if (n <= ws.small_max(K)) {   // small call: ONE launch, one workgroup per item; the expanded dk lives in LDS only (mlkem_small.hpp)
+        const int rate = ws.fips ? 136 : 168;
+#define MLKEM_DSS(JR, NW) launch("k_decaps_seed_small", k_decaps_seed_small<K, ETA1, DU, DV, JR, NW>, n, WAVE * NW, st, n, seed, c, Kout, rate)
+        // eight waves up to small_lat_max, four above (as decaps_run, without its twelve-wave form: at 168 VGPRs the fused kernel spills)
+#define MLKEM_DSS2(JR) do { if (n <= ws.small_lat_max) MLKEM_DSS(JR, SMALL_WAVES); else MLKEM_DSS(JR, SMALL_WAVES_DENSE); } while (0)
+        if (!ws.fips) MLKEM_DSS2(168);
+        else MLKEM_DSS2(136);
+#undef MLKEM_DSS2
+#undef MLKEM_DSS
+        return;
+    }
+    // larger calls: the batch KeyGen into the staging region, then the batch Decaps from it without the hash check (dk is
+    // consistent by construction), one staging chunk at a time
+    for (size_t s0 = 0; s0 < n; s0 += stage_items) {
+        const size_t sn = min_sz(stage_items, n - s0);
+        uint8_t *d = stage, *z = d + stage_items * 32, *ek = z + stage_items * 32, *dk = ek + stage_items * p.ek_len;
+        launch("k_seed_split", k_seed_split, ceil_div(4 * sn, 256), 256, st, sn, reinterpret_cast<const uint4*>(seed + s0 * 64),
+               reinterpret_cast<uint4*>(d), reinterpret_cast<uint4*>(z));
+        keygen_run<K, ETA1>(st, p, sn, d, z, ek, dk, ws);
+        decaps_run<K, ETA1, DU, DV>(st, p, sn, dk, c + s0 * p.c_len, Kout + s0 * 32, nullptr, /*hash_check=*/false, ws);
+    }
+}
+
 // ---- shared-key batches: ONE encapsulation key (encaps) or ONE decapsulation key (decaps) for all n items -----------
 // Same bytes as the per-item calls on replicated keys, but H(ek), the dk hash check and the k x k matrix (9 of the 44 /
 // 36 of the 51 Keccak-f per item at k = 3 ... plus H: 35 / 36) are computed once instead of n times.
@@ -525,6 +556,19 @@ inline int decaps_dispatch(stream_t st, int set, size_t n, const uint8_t* dk, co
     case 512: decaps_run<2, 3, 10, 4>(st, p, n, dk, c, K, status, hash_check, ws); break;
     case 768: decaps_run<3, 2, 10, 4>(st, p, n, dk, c, K, status, hash_check, ws); break;
     default: decaps_run<4, 2, 11, 5>(st, p, n, dk, c, K, status, hash_check, ws); break;
+    }
+    return 0;
+}
+
+// stage / stage_items: see decaps_seed_run (unused by calls of at most small_max items)
+inline int decaps_seed_dispatch(stream_t st, int set, size_t n, const uint8_t* seed, const uint8_t* c, uint8_t* K, uint8_t* stage,
+                                size_t stage_items, const Workspace& ws) {
+    ParamSet p;
+    if (!param_set(set, p)) return -1;
+    switch (set) {
+    case 512: decaps_seed_run<2, 3, 10, 4>(st, p, n, seed, c, K, stage, stage_items, ws); break;
+    case 768: decaps_seed_run<3, 2, 10, 4>(st, p, n, seed, c, K, stage, stage_items, ws); break;
+    default: decaps_seed_run<4, 2, 11, 5>(st, p, n, seed, c, K, stage, stage_items, ws); break;
     }
     return 0;
 }

@@ -17,6 +17,7 @@
 //                                                                                             (ml_kem.c:1310-1359, :1136-1225)
 //   k_keygen_small  wave 0: (rho, sigma) = G(d || k) ; barrier ; jobs: A-hat and the 2k PRF rows ; barrier ;
 //                   wave 0: K-PKE.KeyGen, then H(ek) and the dk tail                          (ml_kem.c:1034-1084, :651-769)
+//   k_decaps_seed_small  Decaps from the 64-byte seed d || z: KeyGen's stages, then Decaps' on the same LDS (see the kernel)
 // Hand-overs are counters in LDS (flag_signal / flag_wait, mlkem_device.hpp), not workgroup barriers: Encaps and Decaps have one
 // barrier, right after the counters are zeroed.  A barrier makes every wave wait for the slowest; here only the consumer of a value
 // waits for its producer, so that J (7 permutations at k = 3, needed by the last instruction of Decaps) delays nothing.
@@ -426,6 +427,160 @@ k_keygen_small(size_t n, const uint8_t* __restrict__ d, const uint8_t* __restric
             if (prim && i < 8) reinterpret_cast<uint2*>(my_dk + 768 * K + 32)[i] = o;
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_decaps_seed_small — Decaps_internal(KeyGen_internal(d, z).dk, c) from the 64-byte seed d || z (FIPS 203 §3.3), one
+// workgroup per item; the expanded dk never leaves LDS
+// ------------------------------------------------------------------------------------------------
+// What the two stages run back to back minus what fusing makes redundant: the re-encryption reads KeyGen's A-hat in LDS
+// transposed (A_T of encrypt1_body) instead of sampling A-hat^T again (k^2 sponges), t-hat is read from the ek bytes KeyGen
+// encoded in LDS (coefficients in [0, q): ByteDecode_12(ByteEncode_12(t-hat)) = t-hat, nothing to check), and there is no
+// H(dk.ek) == dk.h check (dk is consistent by construction).
+//   wave 0: (rho, sigma) = G(d || k) ; barrier ; jobs: A-hat and the 2k PRF rows of s, e ; barrier ;
+//   wave 0: K-PKE.KeyGen into LDS (ek, s-hat), ek_ready | m' = K-PKE.Decrypt, then -- waiting for h_ready -- (K', r') = G(m' || h),
+//           r_ready | c' = Encrypt once the 2k + 1 PRF rows are in, K = c == c' ? K' : Kbar, then it zeroes the secret-bearing LDS
+//   wave 1: Kbar = J(z || c), kbar_ready      wave 2: h = H(ek) once ek_ready, h_ready
+//   waves 1 .. NW - 1: the re-encryption's PRF rows n = w - 1, w - 1 + (NW - 1), ... once r_ready
+// Eight waves at most: twelve (SMALL_WAVES_WIDE, 168 VGPRs) spill at k = 3 and 4 -- KeyGen's whole-matrix prefetch on top of Decaps.
+template <int K>
+struct __attribute__((aligned(16))) SeedLds {
+    uint8_t ek[384 * K + 32];   // ByteEncode_12(t-hat) || rho
+    uint8_t s[384 * K];         // dk_pke = ByteEncode_12(s-hat)
+    uint8_t h[32];              // H(ek)
+};
+struct SeedSync {
+    SmallSync kg;    // KeyGen's jobs: A-hat and the PRF rows of s, e (r_ready: sigma, set from the start)
+    SmallSync enc;   // the re-encryption's PRF rows (jobs_done; r_ready: r'), kbar_ready ; next_job unused (rows are dealt out in a fixed order)
+    uint32_t ek_ready, h_ready;
+};
+
+// `obj` := 0 by the 64 lanes of the calling wave (sizeof(T) a multiple of 16)
+template <class T>
+__device__ __forceinline__ void wave_zero_lds(T& obj) {
+    static_assert(sizeof(T) % 16 == 0, "whole 16-byte stores");
+    uint4 z;
+    z.x = 0; z.y = 0; z.z = 0; z.w = 0;
+    uint4* p = reinterpret_cast<uint4*>(&obj);
+    constexpr unsigned N = (unsigned)(sizeof(T) / 16);
+#pragma unroll 1
+    for (unsigned o0 = 0; o0 < N; o0 += WAVE) {   // scalar trip count: no EXEC-mask loop
+        const unsigned o = o0 + (unsigned)lane_id();
+        if (o < N) p[o] = z;
+    }
+}
+
+template <int K, int ETA1, int DU, int DV, int JRATE, int NW>
+__global__ void __launch_bounds__(WAVE * NW)
+k_decaps_seed_small(size_t n, const uint8_t* __restrict__ seed, const uint8_t* __restrict__ c, uint8_t* __restrict__ Kout, int prf_rate) {
+    static_assert(NW >= 4, "roles of waves 0, 1 and 2");
+    __shared__ K2Lds<K + 1> xl;
+    __shared__ SmallHand<K, ETA1> hand;          // A: A-hat (KeyGen's order) ; prf: s, e rows, then the re-encryption's ; r: sigma, then r'
+    __shared__ SeedLds<K> kl;
+    __shared__ uint32_t sq[NW][XOF_LDS_WORDS];
+    __shared__ uint2 rc_tables[NW][WK_RC_ENTRIES];
+    __shared__ SeedSync sy;
+    constexpr unsigned EK = 384 * K + 32, CLEN = 32 * (DU * K + DV);
+    const int wv = wave_id();
+    const size_t item = blockIdx.x;
+    if (item >= n) return;
+    const uint8_t* my_seed = seed + item * 64;
+    const uint8_t* my_c = c + item * CLEN;
+    WkLane cst;
+    wk_lane_init(cst, rc_tables[wave_id()]);
+    const int i = wk_index();
+    const bool prim = wk_primary();
+    if (wv == 0) {                                   // (rho, sigma) = G(d || k)   (ml_kem.c:674-681)
+        WkState a;
+        a.lo = 0; a.hi = 0;
+        if (i >= 0 && i < 4) {
+            const uint2 v = reinterpret_cast<const uint2*>(my_seed)[i];
+            a.lo = v.x; a.hi = v.y;
+        }
+        if (i == 4) a.lo = (unsigned)K | (0x06u << 8);
+        if (i == 8) a.hi = 0x80000000u;
+        wk_permute(a, cst);
+        uint2 o;
+        o.x = a.lo; o.y = a.hi;
+        if (prim && i < 4) reinterpret_cast<uint2*>(hand.rho)[i] = o;
+        else if (prim && i < 8) reinterpret_cast<uint2*>(hand.r)[i - 4] = o;
+    }
+    if (threadIdx.x == 0) {
+        sy.kg.next_job = 0; sy.kg.jobs_done = 0; sy.kg.r_ready = 1; sy.kg.kbar_ready = 0;   // sigma is ready behind the barrier
+        sy.enc.next_job = 0; sy.enc.jobs_done = 0; sy.enc.r_ready = 0; sy.enc.kbar_ready = 0;
+        sy.ek_ready = 0; sy.h_ready = 0;
+    }
+    block_barrier();
+    // A-hat[a][b] = SampleNTT(rho || b || a) (ml_kem.c:686-693) and the 2k PRF rows (s: n = 0..k-1, e: n = k..2k-1, all eta1)
+    small_jobs<K, ETA1, ETA1>(sy.kg, cst, hand.rho, /*transpose=*/false, hand.A, hand.r, hand.prf, 2 * K, (unsigned)prf_rate, sq[wv]);
+    block_barrier();
+    if (wv == 0) {
+        // K-PKE.KeyGen (ml_kem.c:696-756): ek = ByteEncode_12(t-hat) || rho and dk_pke = ByteEncode_12(s-hat), both into LDS
+        keygen2_body<K, ETA1, false>(xl.xch, 0, 1, hand.A, hand.prf, hand.rho, kl.ek, kl.s);
+        wave_global_fence();
+        flag_signal(&sy.ek_ready);
+        decrypt4_body<K, DU, DV>(0, 1, kl.s, (size_t)(384 * K), my_c, hand.m);   // m' = K-PKE.Decrypt(dk_pke, c)
+        wave_global_fence();
+        flag_wait(&sy.h_ready, 1u);
+        uint2 v;                                     // (K', r') = G(m' || h)
+        v.x = 0; v.y = 0;
+        if (i >= 0 && i < 4) v = reinterpret_cast<const uint2*>(hand.m)[i];
+        else if (i >= 4 && i < 8) v = reinterpret_cast<const uint2*>(kl.h)[i - 4];
+        WkState a;
+        a.lo = v.x; a.hi = v.y;
+        if (i == 8) { a.lo = 0x06u; a.hi = 0x80000000u; }
+        wk_permute(a, cst);
+        uint2 o;
+        o.x = a.lo; o.y = a.hi;
+        if (prim && i < 4) reinterpret_cast<uint2*>(hand.Kp)[i] = o;
+        else if (prim && i < 8) reinterpret_cast<uint2*>(hand.r)[i - 4] = o;
+        flag_signal(&sy.enc.r_ready);
+    } else if (wv == 1) {                            // Kbar = J(z || c): only the final select waits for it
+        WkState a;
+        wk_absorb<JRATE, 0x1F>(a, cst, my_seed + 32, 32, my_c, 32 + CLEN);
+        uint2 o;
+        o.x = a.lo; o.y = a.hi;
+        if (prim && i < 4) reinterpret_cast<uint2*>(hand.Kbar)[i] = o;
+        flag_signal(&sy.enc.kbar_ready);
+    } else if (wv == 2) {                            // h = H(ek), beside Decrypt on wave 0
+        flag_wait(&sy.ek_ready, 1u);
+        WkState a;
+        wk_H(a, cst, kl.ek, EK);
+        uint2 o;
+        o.x = a.lo; o.y = a.hi;
+        if (prim && i < 4) reinterpret_cast<uint2*>(kl.h)[i] = o;
+        flag_signal(&sy.h_ready);
+    }
+    // the re-encryption's 2k + 1 PRF rows (eta1 for n < k, eta2 after), which wait for r': dealt out to waves 1 .. NW - 1 in a fixed
+    // order (a job counter here -- after the role branches -- made the compiler wrap the loop in EXEC-mask bookkeeping)
+    if (wv != 0) {
+        constexpr unsigned PS = (ETA1 == 3) ? 192 : 128;
+#pragma unroll 1
+        for (unsigned row = (unsigned)wv - 1; row < (unsigned)(2 * K + 1); row += NW - 1) {
+            flag_wait(&sy.enc.r_ready, 1u);
+            wk_prf(cst, hand.r, row, row < (unsigned)K ? (unsigned)ETA1 : 2u, (unsigned)prf_rate, hand.prf + row * PS);
+            flag_signal(&sy.enc.jobs_done);
+        }
+        return;
+    }
+    flag_wait(&sy.enc.jobs_done, (uint32_t)(2 * K + 1));
+    encrypt1_body<K, ETA1, DU, DV, true, /*A_T=*/true>(xl.xch, kl.ek, hand.m, hand.A, hand.prf, nullptr, my_c, hand.Kp, hand.Kbar,
+                                                       Kout + item * 32, nullptr, &sy.enc.kbar_ready);
+    // wave 0 is the last reader of every region; the others are through (their last writes are behind the counters it waited for).
+    // sigma, s / s-hat and e (prf rows, dk_pke, the NTT exchange), r', m', K', Kbar and the squeezed blocks go to zero; the
+    // counters stay (a late take_job of another wave must still see the jobs as gone).  The fence: every lane's reads of K' and Kbar
+    // for the select are done before any lane overwrites them
+    wave_lds_fence();
+    wave_zero_lds(hand);
+    wave_zero_lds(kl);
+    wave_zero_lds(xl);
+    wave_zero_lds(sq);
+#ifdef MLKEM_EMU_LDS_PROBE
+    if (lane_id() == 0) {   // one report per workgroup (under the emulator every lane is a host thread of its own)
+        MLKEM_EMU_LDS_PROBE(&hand, sizeof hand); MLKEM_EMU_LDS_PROBE(&kl, sizeof kl);
+        MLKEM_EMU_LDS_PROBE(&xl, sizeof xl); MLKEM_EMU_LDS_PROBE(&sq, sizeof sq);
+    }
+#endif
 }
 
 }   // namespace mlkem

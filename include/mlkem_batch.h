@@ -112,6 +112,15 @@ MLKEM_API int mlkem_encaps_status_dev(mlkem_ctx* ctx, int param_set, size_t n, c
  * `status` may be NULL (check skipped = Decaps_internal semantics). */
 MLKEM_API int mlkem_decaps_dev(mlkem_ctx* ctx, int param_set, size_t n, const uint8_t* dk, const uint8_t* c, uint8_t* K, int32_t* status,
                      void* stream);
+/* Decapsulation from the 64-byte SEED FORMAT of the decapsulation key (FIPS 203 §3.3: d || z stored in place of dk):
+ *   K_i = Decaps_internal(KeyGen_internal(d_i, z_i).dk, c_i); seed : n x 64 (d || z), c : n x c_len, K : n x 32
+ * bit-identical to mlkem_keygen_dev followed by mlkem_decaps_dev (status NULL) on a context of the same conformance mode;
+ * no hash check and no status (the expanded dk is consistent by construction); implicit rejection as in Decaps.
+ * Calls of at most small_max items (1536 / 768 / 512) are ONE launch, one workgroup per item: the expanded dk, sigma, m', K'
+ * and K-bar live in LDS only, and the workgroup zeroes that LDS before it exits.  Larger calls expand the keys chunk by chunk
+ * into a staging region the context allocates with its first such call (chunk_items x 4800 bytes: one chunk of ML-KEM-1024),
+ * zeroes after every call and frees with the context. */
+MLKEM_API int mlkem_decaps_seed_dev(mlkem_ctx* ctx, int param_set, size_t n, const uint8_t* seed, const uint8_t* c, uint8_t* K, void* stream);
 
 /* ---- shared-key batches, device pointers ---------------------------------------------------------------------------
  * n encapsulations to ONE encapsulation key / n decapsulations under ONE decapsulation key (a server's long-lived key):
@@ -211,6 +220,8 @@ MLKEM_API int mlkem_selftest(mlkem_ctx* ctx, int which, unsigned long long* viol
 MLKEM_API int mlkem_keygen(int param_set, size_t n, const uint8_t* d, const uint8_t* z, uint8_t* ek, uint8_t* dk);
 MLKEM_API int mlkem_encaps(int param_set, size_t n, const uint8_t* ek, const uint8_t* m, uint8_t* c, uint8_t* K);
 MLKEM_API int mlkem_decaps(int param_set, size_t n, const uint8_t* dk, const uint8_t* c, uint8_t* K, int32_t* status);
+/* mlkem_decaps_seed_dev over host pointers */
+MLKEM_API int mlkem_decaps_seed(int param_set, size_t n, const uint8_t* seed, const uint8_t* c, uint8_t* K);
 MLKEM_API int mlkem_ntt(size_t n, const uint16_t* f, uint16_t* f_hat);
 MLKEM_API int mlkem_intt(size_t n, const uint16_t* f_hat, uint16_t* f);
 /* SampleNTT (ml_kem.c:189-245) and SamplePolyCBD (ml_kem.c:253-275) over host buffers: n x 34 seed bytes /
