@@ -21,6 +21,13 @@ SHIM_PATH = os.path.join(HERE, "libml_kem.so")
 
 SIZES = {512: (800, 1632, 768), 768: (1184, 2400, 1088), 1024: (1568, 3168, 1568)}  # ek, dk, c (ml_kem.h:52-59)
 ERR_HASH = -5
+# per-item result bits of MLKEM.check_keys / mlkem_check_keys[_dev] (include/mlkem_batch.h); 0 = every requested check passed
+KEYCHECK_EK_MODULUS = 1     # ek: a ByteDecode_12 coefficient >= q (FIPS 203 §7.2)
+KEYCHECK_DK_MODULUS = 2     # the ek embedded in dk: a coefficient >= q
+KEYCHECK_DK_HASH = 4        # H(dk.ek) != dk.h (FIPS 203 §7.3)
+KEYCHECK_EK_MISMATCH = 8    # dk.ek != ek
+KEYCHECK_SEED = 16          # KeyGen_internal(d, z) != (ek, dk)
+KEYCHECK_PCT = 32           # pair-wise consistency test failed
 
 # every symbol include/mlkem_batch.h declares (checked by tests/test_abi.py without a GPU)
 ABI_SYMBOLS = (
@@ -43,6 +50,7 @@ ABI_SYMBOLS = (
     "mlkem_keygen_multi_dev", "mlkem_encaps_multi_dev", "mlkem_decaps_multi_dev", "mlkem_multi_sync", "mlkem_multi_stream", "mlkem_stream_last_staged",
     "mlkem_vector_multiply_dev", "mlkem_poly_add_dev", "mlkem_poly_sub_dev",
     "mlkem_decaps_seed_dev", "mlkem_decaps_seed",
+    "mlkem_check_keys_dev", "mlkem_check_keys",
 )
 SHIM_SYMBOLS = ("init", "KEM_KeyGen", "KEM_Encaps", "KEM_Decaps", "ml_errno", "sha3_b", "sha3_h", "sha3_s", "h2b", "b2h",
                 "SampleNTT", "SamplePolyCBD", "NTT", "InverseNTT")
@@ -83,6 +91,8 @@ def load_library():
     L.mlkem_decaps_dev.argtypes = [vp, i32, sz, vp, vp, vp, vp, vp]
     L.mlkem_decaps_seed_dev.argtypes = [vp, i32, sz, vp, vp, vp, vp]
     L.mlkem_decaps_seed.argtypes = [i32, sz, vp, vp, vp]
+    L.mlkem_check_keys_dev.argtypes = [vp, i32, sz, vp, vp, vp, vp, vp, vp]
+    L.mlkem_check_keys.argtypes = [i32, sz, vp, vp, vp, vp, vp]
     L.mlkem_encaps_status_dev.argtypes = [vp, i32, sz, vp, vp, vp, vp, vp, vp]
     L.mlkem_ctx_set_conformance.argtypes = [vp, i32]
     L.mlkem_ctx_debug_stages.argtypes = [vp, C.c_uint]
@@ -310,6 +320,25 @@ class MLKEM:
         self._check(self.lib.mlkem_decaps_seed_dev(self._ctx, self.param_set, n, seed.data_ptr(), c.data_ptr(), K.data_ptr(),
                                                    self._stream()))
         return K
+
+    def check_keys(self, ek=None, dk=None, seed=None, m=None, status=None):
+        """Batched key validation: ek [n,ek_len] and / or dk [n,dk_len], optionally seed [n,64] = d || z (seed consistency) and
+        m [n,32] (pair-wise consistency test, needs dk) -> int32 status [n] of KEYCHECK_* bits, 0 = every requested check passed.
+        The modulus and hash checks follow FIPS 203 in both conformance modes; the seed and PCT legs use this engine's mode."""
+        torch = self.torch
+        if ek is None and dk is None:
+            raise MLKEMError(-101, "check_keys needs ek or dk")
+        if m is not None and dk is None:
+            raise MLKEMError(-101, "the pair-wise consistency test (m) needs dk")
+        args = [None if t is None else self._dev(t, torch.uint8, w)
+                for t, w in ((ek, self.ek_len), (dk, self.dk_len), (seed, 64), (m, 32))]
+        n = next(t.shape[0] for t in args if t is not None)
+        if any(t is not None and t.shape[0] != n for t in args):
+            raise MLKEMError(-101, "ek, dk, seed and m batch sizes differ")
+        status = self._out(n, None, torch.int32, given=status)
+        ptr = [None if t is None else t.data_ptr() for t in args]
+        self._check(self.lib.mlkem_check_keys_dev(self._ctx, self.param_set, n, *ptr, status.data_ptr(), self._stream()))
+        return status
 
     # reference-style aliases
     KeyGen_internal = keygen

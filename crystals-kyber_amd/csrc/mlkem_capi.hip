@@ -65,9 +65,10 @@ struct mlkem_ctx {
     // to its own context instead (stream_op).
     bool side_allowed = true;
     hipStream_t own_side = nullptr;
-    // staging of seed-format Decaps calls above small_max (decaps_seed_run: d, z, ek, dk per item), chunk_items items of ML-KEM-1024
-    // (4800 bytes each).  Allocated with the first such call, not with the context: the scratch every context carries does not grow for a call type most never make.  Zeroed after
-    // every call and before it is freed.
+    // staging of seed-format Decaps calls above small_max (decaps_seed_run: d, z, ek, dk per item) and of the seed / PCT legs of key
+    // validation (check_keys_run): max(chunk_items, 2) items of ML-KEM-1024 (4800 bytes each; two so that every leg of one key check
+    // fits).  Allocated with the first such call, not with the context: the scratch every context carries does not grow for a call
+    // type most never make.  Zeroed after every call and before it is freed.
     uint8_t* seed_stage = nullptr;
     size_t seed_stage_bytes = 0;
 };
@@ -89,6 +90,21 @@ static void ctx_arm_side(mlkem_ctx* ctx, size_t n) {
 static bool ctx_ok(const mlkem_ctx* ctx) {
     int cur = -1;
     return ctx && hipGetDevice(&cur) == hipSuccess && cur == ctx->device;
+}
+
+// the staging region of mlkem_decaps_seed_dev and mlkem_check_keys_dev: once, for a whole chunk of the largest parameter set (at
+// least two items, so that every leg of a key check fits one item); no later call reallocates (or synchronises)
+static bool ctx_seed_stage(mlkem_ctx* ctx) {
+    if (ctx->seed_stage) return true;
+    ParamSet p4;
+    (void)param_set(1024, p4);
+    const size_t bytes = std::max(ctx->ws.cap, (size_t)2) * seed_stage_bytes(p4);
+    if (!hip_ok(hipMalloc(&ctx->seed_stage, bytes), "hipMalloc(seed staging)")) {
+        ctx->seed_stage = nullptr;
+        return false;
+    }
+    ctx->seed_stage_bytes = bytes;
+    return true;
 }
 
 extern "C" {
@@ -389,20 +405,30 @@ int mlkem_decaps_seed_dev(mlkem_ctx* ctx, int set, size_t n, const uint8_t* seed
         HIP_TRY(hipGetLastError());
         return MLKEM_OK;
     }
-    if (!ctx->seed_stage) {   // once, for a whole chunk of the largest parameter set: no later call reallocates (or synchronises)
-        ParamSet p4;
-        (void)param_set(1024, p4);
-        const size_t bytes = ctx->ws.cap * seed_stage_bytes(p4);
-        if (!hip_ok(hipMalloc(&ctx->seed_stage, bytes), "hipMalloc(seed staging)")) {
-            ctx->seed_stage = nullptr;
-            return MLKEM_ERR_ALLOC;
-        }
-        ctx->seed_stage_bytes = bytes;
-    }
+    if (!ctx_seed_stage(ctx)) return MLKEM_ERR_ALLOC;
     const size_t stage_items = std::min(n, ctx->ws.cap), used = stage_items * seed_stage_bytes(p);
     ctx_arm_side(ctx, stage_items);
     decaps_seed_dispatch(st, set, n, seed, c, K, ctx->seed_stage, stage_items, ctx->ws);
     HIP_TRY(hipMemsetAsync(ctx->seed_stage, 0, used, st));   // after the call's last reader, in stream order
+    HIP_TRY(hipGetLastError());
+    return MLKEM_OK;
+}
+
+int mlkem_check_keys_dev(mlkem_ctx* ctx, int set, size_t n, const uint8_t* ek, const uint8_t* dk, const uint8_t* seed, const uint8_t* m,
+                         int32_t* status, void* stream) {
+    ParamSet p;
+    if (!param_set(set, p)) return MLKEM_ERR_PARAM_SET;
+    if (!ctx_ok(ctx) || (n && (!status || (!ek && !dk) || (m && !dk)))) return MLKEM_ERR_ARG;
+    if (!aligned16(ek) || !aligned16(dk) || !aligned16(seed) || !aligned16(m) || (reinterpret_cast<uintptr_t>(status) & 3u)) return MLKEM_ERR_ARG;
+    if (n == 0) return MLKEM_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool legs = seed || m;
+    if (legs && !ctx_seed_stage(ctx)) return MLKEM_ERR_ALLOC;
+    const size_t chunk = check_chunk_items(p, n, ek != nullptr, seed != nullptr, m != nullptr, ctx->seed_stage_bytes, ctx->ws);
+    if (legs) ctx_arm_side(ctx, chunk);
+    check_keys_dispatch(st, set, n, ek, dk, seed, m, status, ctx->seed_stage, chunk, ctx->ws);
+    if (legs)   // d, z, the expanded keys, K and K': after the call's last reader, in stream order
+        HIP_TRY(hipMemsetAsync(ctx->seed_stage, 0, chunk * check_stage_bytes(p, ek != nullptr, seed != nullptr, m != nullptr), st));
     HIP_TRY(hipGetLastError());
     return MLKEM_OK;
 }
@@ -999,10 +1025,33 @@ int guarded(Fn fn) {
     }
 }
 
-// the three KEM operations as (spans, launch) pairs for stream_op
+// key validation (op 4 of kem_stream): its four optional inputs travel in `a` as one record; the inputs a call leaves out get no span
+struct CheckKeysArgs { const uint8_t *ek, *dk, *seed, *m; };
+int check_keys_stream(StreamEngine& e, int set, size_t n, const CheckKeysArgs& in, int32_t* status, size_t chunk, bool pre_locked) {
+    ParamSet p;
+    if (!param_set(set, p)) return MLKEM_ERR_PARAM_SET;
+    if (n && (!status || (!in.ek && !in.dk) || (in.m && !in.dk))) return MLKEM_ERR_ARG;
+    const uint8_t* ptr[4] = {in.ek, in.dk, in.seed, in.m};
+    const size_t width[4] = {p.ek_len, p.dk_len, 64, 32};
+    int slot[4];
+    std::vector<Span> sp;
+    for (int j = 0; j < 4; j++) {
+        slot[j] = ptr[j] ? (int)sp.size() : -1;
+        if (ptr[j]) sp.push_back({ptr[j], nullptr, width[j]});
+    }
+    const size_t out = sp.size();
+    sp.push_back({nullptr, status, 4});
+    return stream_op(e, n, chunk, sp, [&](mlkem_ctx* ctx, size_t cnt, const std::vector<void*>& v, hipStream_t st) {
+        auto arg = [&](int j) { return slot[j] < 0 ? (const uint8_t*)nullptr : (const uint8_t*)v[slot[j]]; };
+        return mlkem_check_keys_dev(ctx, set, cnt, arg(0), arg(1), arg(2), arg(3), (int32_t*)v[out], st);
+    }, pre_locked);
+}
+
+// the KEM operations as (spans, launch) pairs for stream_op: 0 keygen, 1 encaps, 2 decaps, 3 decaps from seeds, 4 key validation
 int kem_stream(StreamEngine& e, int op, int set, size_t n, const void* a, const void* b, void* x, void* y, size_t chunk, bool pre_locked = false) {
     ParamSet p;
     if (!param_set(set, p)) return MLKEM_ERR_PARAM_SET;
+    if (op == 4) return check_keys_stream(e, set, n, *static_cast<const CheckKeysArgs*>(a), static_cast<int32_t*>(x), chunk, pre_locked);
     if (n && (!a || !b || !x || (!y && op != 3))) return MLKEM_ERR_ARG;
     if (op == 3) {   // decaps from seeds: seed, c -> K
         std::vector<Span> sp = {{a, nullptr, 64}, {b, nullptr, p.c_len}, {nullptr, x, 32}};
@@ -1167,6 +1216,17 @@ int mlkem_decaps_seed(int set, size_t n, const uint8_t* seed, const uint8_t* c, 
         HostRef hs = host_state_current();
         if (!hs) return MLKEM_ERR_NO_DEVICE;
         return kem_on_free_engine(hs.get(), 3, set, n, seed, c, K, nullptr, 0);
+    });
+}
+int mlkem_check_keys(int set, size_t n, const uint8_t* ek, const uint8_t* dk, const uint8_t* seed, const uint8_t* m, int32_t* status) {
+    ParamSet p;
+    if (!param_set(set, p)) return MLKEM_ERR_PARAM_SET;
+    if (n && (!status || (!ek && !dk) || (m && !dk))) return MLKEM_ERR_ARG;
+    return guarded([&]() -> int {   // an engine lane of the current device, like mlkem_decaps_seed (no combining)
+        HostRef hs = host_state_current();
+        if (!hs) return MLKEM_ERR_NO_DEVICE;
+        const CheckKeysArgs in{ek, dk, seed, m};
+        return kem_on_free_engine(hs.get(), 4, set, n, &in, nullptr, status, nullptr, 0);
     });
 }
 int mlkem_keygen_stream(int set, size_t n, const uint8_t* d, const uint8_t* z, uint8_t* ek, uint8_t* dk, size_t chunk_items) {

@@ -19,6 +19,7 @@
 #include "mlkem_kpke2.hpp"
 #include "mlkem_wkeccak.hpp"
 #include "mlkem_small.hpp"
+#include "mlkem_check.hpp"
 #include <stdlib.h>
 #ifndef MLKEM_EMU
 #include <vector>
@@ -426,6 +427,69 @@ inline void decaps_seed_run(stream_t st, const ParamSet& p, size_t n, const uint
     }
 }
 
+// ---- key validation (FIPS 203 §7.2 / §7.3, seed consistency, pair-wise consistency test): status bits of mlkem_check.hpp ----
+// Staging bytes per item of the legs a call asks for: the seed leg holds d, z and KeyGen's ek, dk; the PCT leg c, K, K' and, for a
+// call without ek, the ek' = dk.ek rows Encaps takes.  The structural check alone stages nothing.
+inline size_t check_stage_bytes(const ParamSet& p, bool has_ek, bool seed, bool pct) {
+    return (seed ? seed_stage_bytes(p) : 0) + (pct ? (size_t)p.c_len + 64 + (has_ek ? 0 : (size_t)p.ek_len) : 0);
+}
+// items per staging round: min(n, cap), fewer where the legs need more than the region holds for cap items (ML-KEM-1024 with
+// both legs: 6432 bytes per item with ek, 8000 without it, against the region's 4800)
+inline size_t check_chunk_items(const ParamSet& p, size_t n, bool has_ek, bool seed, bool pct, size_t stage_bytes, const Workspace& ws) {
+    const size_t need = check_stage_bytes(p, has_ek, seed, pct);
+    size_t c = min_sz(n, ws.cap);
+    if (need) c = min_sz(c, stage_bytes / need);
+    return c ? c : 1;
+}
+// ek / dk: n rows or nullptr (at least one given); seed (n x 64, d || z): the seed leg; m (n x 32, needs dk): the PCT to ek' = ek,
+// else dk.ek.  `stage` holds `chunk` items of check_stage_bytes (check_chunk_items); the caller owns it and zeroes it after the call.
+// Per chunk: k_seed_split -> KeyGen (seed leg), Encaps -> Decaps without the hash check (PCT leg), then ONE k_check_keys; above
+// ws.wide_kem(K) items H(dk.ek) comes from the lane-sliced k_hash_batch<0> into ws.Kp first (the crossover of the KEM paths).
+template <int K, int ETA1, int DU, int DV>
+inline void check_keys_run(stream_t st, const ParamSet& p, size_t n, const uint8_t* ek, const uint8_t* dk, const uint8_t* seed,
+                           const uint8_t* m, int32_t* status, uint8_t* stage, size_t chunk, const Workspace& ws) {
+    if (n == 0) return;
+    const bool hash_in = n <= ws.wide_kem(K);
+    for (size_t s0 = 0; s0 < n; s0 += chunk) {
+        const size_t sn = min_sz(chunk, n - s0);
+        const uint8_t* eki = ek ? ek + s0 * p.ek_len : nullptr;
+        const uint8_t* dki = dk ? dk + s0 * p.dk_len : nullptr;
+        const uint8_t *sek = nullptr, *sdk = nullptr, *Kc = nullptr, *Kd = nullptr;
+        uint8_t* q = stage;
+        if (seed) {
+            uint8_t *d = q, *z = d + chunk * 32, *e2 = z + chunk * 32, *d2 = e2 + chunk * p.ek_len;
+            q = d2 + chunk * p.dk_len;
+            launch("k_seed_split", k_seed_split, ceil_div(4 * sn, 256), 256, st, sn, reinterpret_cast<const uint4*>(seed + s0 * 64),
+                   reinterpret_cast<uint4*>(d), reinterpret_cast<uint4*>(z));
+            keygen_run<K, ETA1>(st, p, sn, d, z, e2, d2, ws);
+            sek = e2;
+            sdk = d2;
+        }
+        if (m) {
+            const uint8_t* pek = eki;
+            if (!ek) {
+                uint8_t* g = q;
+                q += chunk * p.ek_len;
+                launch("k_gather_rows", k_gather_rows, ceil_div(sn * (p.ek_len / 16), 256), 256, st, sn, dki + 384 * K, (size_t)p.dk_len, g,
+                       (unsigned)p.ek_len);
+                pek = g;
+            }
+            uint8_t *c = q, *kc = c + chunk * p.c_len, *kd = kc + chunk * 32;
+            encaps_run<K, ETA1, DU, DV>(st, p, sn, pek, m + s0 * 32, c, kc, nullptr, ws);
+            decaps_run<K, ETA1, DU, DV>(st, p, sn, dki, c, kd, nullptr, /*hash_check=*/false, ws);
+            Kc = kc;
+            Kd = kd;
+        }
+        if (hash_in) {
+            launch("k_check_keys", k_check_keys<K, true>, sn, 2 * WAVE, st, sn, eki, dki, (const uint8_t*)nullptr, sek, sdk, Kc, Kd, status + s0);
+        } else {
+            if (dki) launch("k_hash_batch", k_hash_batch<0>, ceil_div(sn, WAVE), WAVE, st, sn, dki + 384 * K, (unsigned)p.ek_len, (size_t)p.dk_len, ws.Kp);
+            launch("k_check_keys", k_check_keys<K, false>, ceil_div(sn, 4), WAVE * 4, st, sn, eki, dki, (const uint8_t*)ws.Kp, sek, sdk, Kc, Kd,
+                   status + s0);
+        }
+    }
+}
+
 // ---- shared-key batches: ONE encapsulation key (encaps) or ONE decapsulation key (decaps) for all n items -----------
 // Same bytes as the per-item calls on replicated keys, but H(ek), the dk hash check and the k x k matrix (9 of the 44 /
 // 36 of the 51 Keccak-f per item at k = 3 ... plus H: 35 / 36) are computed once instead of n times.
@@ -569,6 +633,19 @@ inline int decaps_seed_dispatch(stream_t st, int set, size_t n, const uint8_t* s
     case 512: decaps_seed_run<2, 3, 10, 4>(st, p, n, seed, c, K, stage, stage_items, ws); break;
     case 768: decaps_seed_run<3, 2, 10, 4>(st, p, n, seed, c, K, stage, stage_items, ws); break;
     default: decaps_seed_run<4, 2, 11, 5>(st, p, n, seed, c, K, stage, stage_items, ws); break;
+    }
+    return 0;
+}
+
+// stage / chunk: see check_keys_run
+inline int check_keys_dispatch(stream_t st, int set, size_t n, const uint8_t* ek, const uint8_t* dk, const uint8_t* seed, const uint8_t* m,
+                               int32_t* status, uint8_t* stage, size_t chunk, const Workspace& ws) {
+    ParamSet p;
+    if (!param_set(set, p)) return -1;
+    switch (set) {
+    case 512: check_keys_run<2, 3, 10, 4>(st, p, n, ek, dk, seed, m, status, stage, chunk, ws); break;
+    case 768: check_keys_run<3, 2, 10, 4>(st, p, n, ek, dk, seed, m, status, stage, chunk, ws); break;
+    default: check_keys_run<4, 2, 11, 5>(st, p, n, ek, dk, seed, m, status, stage, chunk, ws); break;
     }
     return 0;
 }

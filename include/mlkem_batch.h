@@ -118,9 +118,29 @@ MLKEM_API int mlkem_decaps_dev(mlkem_ctx* ctx, int param_set, size_t n, const ui
  * no hash check and no status (the expanded dk is consistent by construction); implicit rejection as in Decaps.
  * Calls of at most small_max items (1536 / 768 / 512) are ONE launch, one workgroup per item: the expanded dk, sigma, m', K'
  * and K-bar live in LDS only, and the workgroup zeroes that LDS before it exits.  Larger calls expand the keys chunk by chunk
- * into a staging region the context allocates with its first such call (chunk_items x 4800 bytes: one chunk of ML-KEM-1024),
+ * into a staging region the context allocates with its first such call (max(chunk_items, 2) x 4800 bytes: one chunk of ML-KEM-1024, at least two items because mlkem_check_keys_dev shares the region
+ * and its legs need up to 8000 bytes for one item),
  * zeroes after every call and frees with the context. */
 MLKEM_API int mlkem_decaps_seed_dev(mlkem_ctx* ctx, int param_set, size_t n, const uint8_t* seed, const uint8_t* c, uint8_t* K, void* stream);
+
+/* ---- key validation -------------------------------------------------------------------------------------------------
+ * Per-item result bits of mlkem_check_keys[_dev]; 0 = every requested check passed.  A bit whose inputs are absent is 0. */
+#define MLKEM_KEYCHECK_EK_MODULUS 1   /* ek: a ByteDecode_12 coefficient >= q                              (FIPS 203 §7.2) */
+#define MLKEM_KEYCHECK_DK_MODULUS 2   /* the ek embedded in dk: a coefficient >= q                         (FIPS 203 §7.2 on dk.ek) */
+#define MLKEM_KEYCHECK_DK_HASH 4      /* H(dk.ek) != dk.h                                                  (FIPS 203 §7.3) */
+#define MLKEM_KEYCHECK_EK_MISMATCH 8  /* dk.ek != ek (both given) */
+#define MLKEM_KEYCHECK_SEED 16        /* KeyGen_internal(d, z) != (ek, dk) on whichever of ek / dk is given */
+#define MLKEM_KEYCHECK_PCT 32         /* Decaps_internal(dk, c) != K for (c, K) = Encaps_internal(ek', m_i) */
+/* Batched key validation: ek n x ek_len or NULL, dk n x dk_len or NULL (at least one of them), seed n x 64 (d || z) or NULL, m n x 32
+ * or NULL (needs dk), status n x int32 (required).  `seed` requests the seed leg; `m` the pair-wise consistency test, which
+ * encapsulates to ek' = ek when given, dk.ek otherwise.  The modulus and hash checks are the FIPS 203 definitions in BOTH
+ * conformance modes (H is SHA3-256 either way); mlkem_encaps_dev on a REFERENCE-mode context still accepts a key that fails the
+ * modulus check.  The seed and PCT legs use the context's mode (PRF, J): they test consistency with this context's KeyGen / Encaps /
+ * Decaps.  The structural check is one launch up to the wave-wide hash limit (the expensive legs are the existing KeyGen / Encaps /
+ * Decaps kernels); the legs stage through the context's region of mlkem_decaps_seed_dev (allocated with the first call that needs it,
+ * zeroed after every call). */
+MLKEM_API int mlkem_check_keys_dev(mlkem_ctx* ctx, int param_set, size_t n, const uint8_t* ek, const uint8_t* dk, const uint8_t* seed,
+                                   const uint8_t* m, int32_t* status, void* stream);
 
 /* ---- shared-key batches, device pointers ---------------------------------------------------------------------------
  * n encapsulations to ONE encapsulation key / n decapsulations under ONE decapsulation key (a server's long-lived key):
@@ -222,6 +242,9 @@ MLKEM_API int mlkem_encaps(int param_set, size_t n, const uint8_t* ek, const uin
 MLKEM_API int mlkem_decaps(int param_set, size_t n, const uint8_t* dk, const uint8_t* c, uint8_t* K, int32_t* status);
 /* mlkem_decaps_seed_dev over host pointers */
 MLKEM_API int mlkem_decaps_seed(int param_set, size_t n, const uint8_t* seed, const uint8_t* c, uint8_t* K);
+/* mlkem_check_keys_dev over host pointers */
+MLKEM_API int mlkem_check_keys(int param_set, size_t n, const uint8_t* ek, const uint8_t* dk, const uint8_t* seed, const uint8_t* m,
+                               int32_t* status);
 MLKEM_API int mlkem_ntt(size_t n, const uint16_t* f, uint16_t* f_hat);
 MLKEM_API int mlkem_intt(size_t n, const uint16_t* f_hat, uint16_t* f);
 /* SampleNTT (ml_kem.c:189-245) and SamplePolyCBD (ml_kem.c:253-275) over host buffers: n x 34 seed bytes /
