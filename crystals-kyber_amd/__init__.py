@@ -21,6 +21,8 @@ SHIM_PATH = os.path.join(HERE, "libml_kem.so")
 
 SIZES = {512: (800, 1632, 768), 768: (1184, 2400, 1088), 1024: (1568, 3168, 1568)}  # ek, dk, c (ml_kem.h:52-59)
 ERR_HASH = -5
+ERR_KEY = -6                # MLKEM_ERR_KEY: a key failed validation, no key set was created (MLKEMError.key_status says which)
+ERR_ARG = -101              # MLKEM_ERR_ARG; also the per-item status of a key-set call whose key index is out of range
 # per-item result bits of MLKEM.check_keys / mlkem_check_keys[_dev] (include/mlkem_batch.h); 0 = every requested check passed
 KEYCHECK_EK_MODULUS = 1     # ek: a ByteDecode_12 coefficient >= q (FIPS 203 §7.2)
 KEYCHECK_DK_MODULUS = 2     # the ek embedded in dk: a coefficient >= q
@@ -51,15 +53,17 @@ ABI_SYMBOLS = (
     "mlkem_vector_multiply_dev", "mlkem_poly_add_dev", "mlkem_poly_sub_dev",
     "mlkem_decaps_seed_dev", "mlkem_decaps_seed",
     "mlkem_check_keys_dev", "mlkem_check_keys",
+    "mlkem_keyset_create", "mlkem_keyset_destroy", "mlkem_keyset_info", "mlkem_encaps_keyset_dev", "mlkem_decaps_keyset_dev",
 )
 SHIM_SYMBOLS = ("init", "KEM_KeyGen", "KEM_Encaps", "KEM_Decaps", "ml_errno", "sha3_b", "sha3_h", "sha3_s", "h2b", "b2h",
                 "SampleNTT", "SamplePolyCBD", "NTT", "InverseNTT")
 
 
 class MLKEMError(RuntimeError):
-    def __init__(self, code, msg):
+    def __init__(self, code, msg, key_status=None):
         super().__init__(f"mlkem error {code}: {msg}")
         self.code = code
+        self.key_status = key_status   # MLKEM.prepare_keys refusals (code ERR_KEY): the KEYCHECK_* bits per key
 
 
 _lib = None
@@ -93,6 +97,12 @@ def load_library():
     L.mlkem_decaps_seed.argtypes = [i32, sz, vp, vp, vp]
     L.mlkem_check_keys_dev.argtypes = [vp, i32, sz, vp, vp, vp, vp, vp, vp]
     L.mlkem_check_keys.argtypes = [i32, sz, vp, vp, vp, vp, vp]
+    L.mlkem_keyset_create.argtypes = [vp, i32, sz, vp, vp, vp, vp, C.POINTER(vp), vp]
+    L.mlkem_keyset_destroy.argtypes = [vp]
+    L.mlkem_keyset_destroy.restype = None
+    L.mlkem_keyset_info.argtypes = [vp, C.POINTER(i32), C.POINTER(sz), C.POINTER(i32), C.POINTER(sz)]
+    L.mlkem_encaps_keyset_dev.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp]
+    L.mlkem_decaps_keyset_dev.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
     L.mlkem_encaps_status_dev.argtypes = [vp, i32, sz, vp, vp, vp, vp, vp, vp]
     L.mlkem_ctx_set_conformance.argtypes = [vp, i32]
     L.mlkem_ctx_debug_stages.argtypes = [vp, C.c_uint]
@@ -339,6 +349,25 @@ class MLKEM:
         ptr = [None if t is None else t.data_ptr() for t in args]
         self._check(self.lib.mlkem_check_keys_dev(self._ctx, self.param_set, n, *ptr, status.data_ptr(), self._stream()))
         return status
+
+    def prepare_keys(self, ek=None, dk=None, seed=None):
+        """A prepared key set (KeySet) from exactly one of ek [n_keys,ek_len], dk [n_keys,dk_len] or seed [n_keys,64] = d || z:
+        validated once (the FIPS 203 modulus and hash checks of check_keys on ek or dk alone), H(ek) and A-hat^T stored on the
+        device.  Raises MLKEMError with code ERR_KEY and a `key_status` tensor (KEYCHECK_* bits per key) when any key fails."""
+        torch = self.torch
+        given = [(t, w) for t, w in ((ek, self.ek_len), (dk, self.dk_len), (seed, 64))]
+        if sum(t is not None for t, _ in given) != 1:
+            raise MLKEMError(-101, "prepare_keys takes exactly one of ek, dk and seed")
+        args = [None if t is None else self._dev(t, torch.uint8, w) for t, w in given]
+        n = next(t.shape[0] for t in args if t is not None)
+        status = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
+        h = C.c_void_p()
+        ptr = [None if t is None else t.data_ptr() for t in args]
+        rc = self.lib.mlkem_keyset_create(self._ctx, self.param_set, n, *ptr, status.data_ptr(), C.byref(h), self._stream())
+        if rc == ERR_KEY:
+            raise MLKEMError(rc, self.lib.mlkem_strerror(rc).decode(), key_status=status[:n])
+        self._check(rc)
+        return KeySet(self, h)
 
     # reference-style aliases
     KeyGen_internal = keygen
@@ -775,3 +804,79 @@ def shard_range(n_total, rank, world):
     base, rem = divmod(n_total, world)
     start = rank * base + min(rank, rem)
     return start, start + base + (1 if rank < rem else 0)
+
+
+class KeySet:
+    """A prepared key set on an engine's device (mlkem_keyset_*): items of encaps / decaps name their key by index.
+    Read-only after creation: any engine (context) of the same parameter set on the same device may use it.  close() (or the
+    end of a `with` block, or garbage collection) synchronises the device, zeroes the tables and frees them."""
+
+    def __init__(self, engine, handle):
+        self._eng = engine
+        self.lib = engine.lib
+        self._h = handle
+        ps, nk, hd, nb = C.c_int(), C.c_size_t(), C.c_int(), C.c_size_t()
+        engine._check(self.lib.mlkem_keyset_info(handle, C.byref(ps), C.byref(nk), C.byref(hd), C.byref(nb)))
+        self.param_set, self.n_keys, self.has_dk, self.device_bytes = ps.value, nk.value, bool(hd.value), nb.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.mlkem_keyset_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _engine(self, engine):
+        eng = engine or self._eng
+        if not self._h:
+            raise MLKEMError(-101, "key set is closed")
+        if eng.param_set != self.param_set:
+            raise MLKEMError(-101, "engine and key set have different parameter sets")
+        return eng
+
+    def _index(self, eng, key_index, n):
+        torch = eng.torch
+        if key_index is None:
+            return None
+        t = key_index if isinstance(key_index, torch.Tensor) else torch.as_tensor(key_index)
+        if t.dtype not in (torch.int32, torch.uint32):
+            raise MLKEMError(-101, "key_index must be an int32 or uint32 tensor")
+        t = t.to(device=eng.device).contiguous().reshape(-1)
+        if t.shape[0] != n:
+            raise MLKEMError(-101, "key_index and the batch have different sizes")
+        return t
+
+    def encaps(self, m, key_index=None, c=None, K=None, return_status=False, engine=None):
+        """Encaps_internal to key key_index[i] for item i (None: key 0): m [n,32] -> c [n,c_len], K [n,32] (+ int32 status [n]:
+        0, or ERR_ARG where the index is out of range -- c and K are then zero)."""
+        eng = self._engine(engine)
+        torch = eng.torch
+        m = eng._dev(m, torch.uint8, 32)
+        n = m.shape[0]
+        idx = self._index(eng, key_index, n)
+        c = eng._out(n, eng.c_len, given=c)
+        K = eng._out(n, 32, given=K)
+        st = torch.empty(n, dtype=torch.int32, device=eng.device) if return_status else None
+        eng._check(self.lib.mlkem_encaps_keyset_dev(eng._ctx, self._h, n, None if idx is None else idx.data_ptr(), m.data_ptr(), c.data_ptr(),
+                                                    K.data_ptr(), None if st is None else st.data_ptr(), eng._stream()))
+        return (c, K, st) if return_status else (c, K)
+
+    def decaps(self, c, key_index=None, K=None, return_status=False, engine=None):
+        """Decaps_internal under key key_index[i] for item i (None: key 0): c [n,c_len] -> K [n,32] (+ int32 status [n]: 0, or
+        ERR_ARG where the index is out of range -- K is then zero).  Needs a set made from dk or seed."""
+        eng = self._engine(engine)
+        torch = eng.torch
+        c = eng._dev(c, torch.uint8, eng.c_len)
+        n = c.shape[0]
+        idx = self._index(eng, key_index, n)
+        K = eng._out(n, 32, given=K)
+        st = torch.empty(n, dtype=torch.int32, device=eng.device) if return_status else None
+        eng._check(self.lib.mlkem_decaps_keyset_dev(eng._ctx, self._h, n, None if idx is None else idx.data_ptr(), c.data_ptr(), K.data_ptr(),
+                                                    None if st is None else st.data_ptr(), eng._stream()))
+        return (K, st) if return_status else K

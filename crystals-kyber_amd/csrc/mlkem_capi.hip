@@ -4,6 +4,7 @@
 // MLKEM_ERR_NO_DEVICE / a HIP error.  The CPU oracle under oracle/ is test infrastructure and is never
 // linked or loaded by this library.
 #include "mlkem_pipeline.hpp"
+#include "mlkem_keyset.hpp"
 #include "mlkem_selftest.hpp"
 
 #include "../../include/mlkem_batch.h"
@@ -71,6 +72,17 @@ struct mlkem_ctx {
     // type most never make.  Zeroed after every call and before it is freed.
     uint8_t* seed_stage = nullptr;
     size_t seed_stage_bytes = 0;
+    KeysetLimits ks_lim;   // dispatch limits of the key-set calls (mlkem_keyset.hpp)
+};
+
+// A prepared key set (mlkem_keyset.hpp): ONE device allocation holding the keys | H(ek) | A-hat^T tables, read-only after
+// mlkem_keyset_create, bound to the device it was created on.
+struct mlkem_keyset {
+    int device = 0;
+    ParamSet p{};
+    KeysetView v;
+    uint8_t* mem = nullptr;
+    size_t bytes = 0;
 };
 
 // called by the *_dev entry points that fork: gives the context its side stream the first time a call fits one chunk
@@ -140,6 +152,7 @@ const char* mlkem_strerror(int code) {
     case MLKEM_ERR_LENGTH: return "type check failed: wrong ek/dk/c length (reference ml_errno -3)";
     case MLKEM_ERR_MODULUS: return "modulus check failed (reference ml_errno -4; unreachable)";
     case MLKEM_ERR_HASH: return "decapsulation key hash check failed (reference ml_errno -5)";
+    case MLKEM_ERR_KEY: return "a key failed validation: no key set was created (see key_status)";
     case MLKEM_ERR_NO_DEVICE: return "no usable HIP device / HIP runtime error (no CPU fallback exists)";
     case MLKEM_ERR_ARG: return "bad argument (NULL or misaligned pointer)";
     case MLKEM_ERR_ALLOC: return "allocation failed";
@@ -205,6 +218,14 @@ int mlkem_ctx_create(mlkem_ctx** out, int device, size_t chunk_items) {
     if (const char* e = getenv("MLKEM_SMALL_LATENCY_ITEMS")) {   // small calls above this size: four waves per item instead of eight
         long long v = atoll(e);
         if (v >= 0) c->ws.small_lat_max = (size_t)v;
+    }
+    if (const char* e = getenv("MLKEM_KEYSET_SMALL_ITEMS")) {     // key-set calls up to this size: one workgroup per item (0: never)
+        long long v = atoll(e);
+        if (v >= 0) c->ks_lim.set_all((size_t)v, (size_t)-1);
+    }
+    if (const char* e = getenv("MLKEM_KEYSET_LATENCY_ITEMS")) {   // ... of which calls up to this size use eight waves per item
+        long long v = atoll(e);
+        if (v >= 0) c->ks_lim.set_all((size_t)-1, (size_t)v);
     }
     // fork / join events of one-chunk calls (SideFork, mlkem_pipeline.hpp); the side stream itself comes with the first such call
     // (ctx_arm_side).  MLKEM_SIDE_STREAM=0 keeps every call on the caller's stream; failing to create the events does the same.
@@ -429,6 +450,123 @@ int mlkem_check_keys_dev(mlkem_ctx* ctx, int set, size_t n, const uint8_t* ek, c
     check_keys_dispatch(st, set, n, ek, dk, seed, m, status, ctx->seed_stage, chunk, ctx->ws);
     if (legs)   // d, z, the expanded keys, K and K': after the call's last reader, in stream order
         HIP_TRY(hipMemsetAsync(ctx->seed_stage, 0, chunk * check_stage_bytes(p, ek != nullptr, seed != nullptr, m != nullptr), st));
+    HIP_TRY(hipGetLastError());
+    return MLKEM_OK;
+}
+
+// ---- prepared key sets (mlkem_keyset.hpp) ----------------------------------------------------------------------------
+static void keyset_free(mlkem_keyset* ks) {   // the tables hold dk and z: zeroed before they are freed
+    if (ks->mem) {
+        (void)hipMemset(ks->mem, 0, ks->bytes);
+        (void)hipFree(ks->mem);
+    }
+    delete ks;
+}
+
+int mlkem_keyset_create(mlkem_ctx* ctx, int set, size_t n_keys, const uint8_t* ek, const uint8_t* dk, const uint8_t* seed,
+                        int32_t* key_status, mlkem_keyset** out, void* stream) {
+    ParamSet p;
+    if (!param_set(set, p)) return MLKEM_ERR_PARAM_SET;
+    if (!out) return MLKEM_ERR_ARG;
+    *out = nullptr;
+    if (!ctx_ok(ctx) || n_keys == 0 || (ek ? 1 : 0) + (dk ? 1 : 0) + (seed ? 1 : 0) != 1) return MLKEM_ERR_ARG;
+    if (!aligned16(ek) || !aligned16(dk) || !aligned16(seed) || (reinterpret_cast<uintptr_t>(key_status) & 3u)) return MLKEM_ERR_ARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool has_dk = ek == nullptr;
+    const size_t key_len = has_dk ? p.dk_len : p.ek_len;
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t szK = up(n_keys * key_len), szH = up(n_keys * 32), szA = up(n_keys * (size_t)(p.k * p.k) * 512);
+    // call-local device memory: the status words when the caller passes none, the refusal word, and a seed import's d, z, ek
+    const size_t szS = key_status ? 0 : up(n_keys * 4), szT = seed ? up(n_keys * (64 + (size_t)p.ek_len)) : 0, tmp_bytes = szS + 256 + szT;
+    mlkem_keyset* ks = new (std::nothrow) mlkem_keyset();
+    if (!ks) return MLKEM_ERR_ALLOC;
+    ks->device = ctx->device;
+    ks->p = p;
+    ks->bytes = szK + szH + szA;
+    if (!hip_ok(hipMalloc(&ks->mem, ks->bytes), "hipMalloc(key set)")) {
+        ks->mem = nullptr;
+        delete ks;
+        return MLKEM_ERR_ALLOC;
+    }
+    uint8_t* tmp = nullptr;
+    if (!hip_ok(hipMalloc(&tmp, tmp_bytes), "hipMalloc(key set import)")) {
+        keyset_free(ks);
+        return MLKEM_ERR_ALLOC;
+    }
+    uint8_t* keys = ks->mem;
+    uint8_t* hs = keys + szK;
+    uint16_t* At = reinterpret_cast<uint16_t*>(hs + szH);
+    int32_t* status = key_status ? key_status : reinterpret_cast<int32_t*>(tmp);
+    uint32_t* status_or = reinterpret_cast<uint32_t*>(tmp + szS);
+    ks->v.keys = keys;
+    ks->v.key_stride = key_len;
+    ks->v.ek_off = has_dk ? 384u * p.k : 0;
+    ks->v.h = hs;
+    ks->v.At = At;
+    ks->v.n_keys = n_keys;
+    ks->v.has_dk = has_dk;
+    uint32_t refused = 0;
+    bool ok = true;
+    if (seed) {   // KeyGen_internal straight into the dk table: consistent by construction, nothing to check
+        keyset_seed_run(st, p, n_keys, seed, keys, tmp + szS + 256, ctx->ws);
+        if (key_status) ok = hip_ok(hipMemsetAsync(key_status, 0, n_keys * 4, st), "hipMemsetAsync(key_status)");
+    } else {      // the checks run on the set's own copy: what was validated is what is used
+        ok = hip_ok(hipMemcpyAsync(keys, ek ? ek : dk, n_keys * key_len, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync(keys)");
+    }
+    if (ok) {
+        keyset_import_dispatch(st, p, ks->v, hs, At, seed ? nullptr : status, status_or, ctx->ws);
+        ok = hip_ok(hipGetLastError(), "key set import") && hip_ok(hipMemcpyAsync(&refused, status_or, 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") &&
+             hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize");
+    }
+    (void)hipMemset(tmp, 0, tmp_bytes);   // d, z of a seed import
+    (void)hipFree(tmp);
+    if (!ok) {
+        keyset_free(ks);
+        return MLKEM_ERR_NO_DEVICE;
+    }
+    if (refused) {
+        keyset_free(ks);
+        return MLKEM_ERR_KEY;
+    }
+    *out = ks;
+    return MLKEM_OK;
+}
+
+void mlkem_keyset_destroy(mlkem_keyset* ks) {
+    if (!ks) return;
+    int prev = -1;
+    (void)hipGetDevice(&prev);
+    (void)hipSetDevice(ks->device);
+    (void)hipDeviceSynchronize();   // no call in flight still reads the tables
+    keyset_free(ks);
+    if (prev >= 0) (void)hipSetDevice(prev);
+}
+
+int mlkem_keyset_info(const mlkem_keyset* ks, int* param_set_out, size_t* n_keys, int* has_dk, size_t* device_bytes) {
+    if (!ks) return MLKEM_ERR_ARG;
+    if (param_set_out) *param_set_out = ks->p.set;
+    if (n_keys) *n_keys = ks->v.n_keys;
+    if (has_dk) *has_dk = ks->v.has_dk ? 1 : 0;
+    if (device_bytes) *device_bytes = ks->bytes;
+    return MLKEM_OK;
+}
+
+int mlkem_encaps_keyset_dev(mlkem_ctx* ctx, const mlkem_keyset* ks, size_t n, const uint32_t* key_index, const uint8_t* m, uint8_t* c,
+                            uint8_t* K, int32_t* status, void* stream) {
+    if (!ks || !ctx_ok(ctx) || ks->device != ctx->device || (n && (!m || !c || !K))) return MLKEM_ERR_ARG;
+    if (!aligned16(key_index) || !aligned16(m) || !aligned16(c) || !aligned16(K) || (reinterpret_cast<uintptr_t>(status) & 3u)) return MLKEM_ERR_ARG;
+    if (n == 0) return MLKEM_OK;
+    encaps_keyset_dispatch(static_cast<hipStream_t>(stream), ks->p, ks->v, n, key_index, m, c, K, status, ctx->ws, ctx->ks_lim);
+    HIP_TRY(hipGetLastError());
+    return MLKEM_OK;
+}
+
+int mlkem_decaps_keyset_dev(mlkem_ctx* ctx, const mlkem_keyset* ks, size_t n, const uint32_t* key_index, const uint8_t* c, uint8_t* K,
+                            int32_t* status, void* stream) {
+    if (!ks || !ctx_ok(ctx) || ks->device != ctx->device || !ks->v.has_dk || (n && (!c || !K))) return MLKEM_ERR_ARG;
+    if (!aligned16(key_index) || !aligned16(c) || !aligned16(K) || (reinterpret_cast<uintptr_t>(status) & 3u)) return MLKEM_ERR_ARG;
+    if (n == 0) return MLKEM_OK;
+    decaps_keyset_dispatch(static_cast<hipStream_t>(stream), ks->p, ks->v, n, key_index, c, K, status, ctx->ws, ctx->ks_lim);
     HIP_TRY(hipGetLastError());
     return MLKEM_OK;
 }

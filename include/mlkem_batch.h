@@ -43,6 +43,7 @@ extern "C" {
 #define MLKEM_ERR_LENGTH (-3)       /* ek/dk/c length mismatch (reference: ml_errno = -3, ml_kem.c:1269, :1323, :1331) */
 #define MLKEM_ERR_MODULUS (-4)      /* never produced: the reference's check is a no-op (ml_kem.c:1273-1291) */
 #define MLKEM_ERR_HASH (-5)         /* per-item status: H(dk.ek) != dk.h (reference: ml_errno = -5, ml_kem.c:1347) */
+#define MLKEM_ERR_KEY (-6)          /* a key failed validation: no key set was created (key_status says which and why) */
 #define MLKEM_ERR_NO_DEVICE (-100)  /* no HIP device / HIP runtime error */
 #define MLKEM_ERR_ARG (-101)        /* NULL or misaligned pointer, bad argument */
 #define MLKEM_ERR_ALLOC (-102)      /* device or host allocation failed */
@@ -141,6 +142,38 @@ MLKEM_API int mlkem_decaps_seed_dev(mlkem_ctx* ctx, int param_set, size_t n, con
  * zeroed after every call). */
 MLKEM_API int mlkem_check_keys_dev(mlkem_ctx* ctx, int param_set, size_t n, const uint8_t* ek, const uint8_t* dk, const uint8_t* seed,
                                    const uint8_t* m, int32_t* status, void* stream);
+
+/* ---- prepared key sets, device pointers -----------------------------------------------------------------------------
+ * A key set is validated once and then serves any number of Encaps / Decaps calls whose items name their key by index.  Per key it
+ * holds the ek or dk bytes, H(ek) and the k x k matrix A-hat^T (k^2 x 256 uint16): about 7.0 KB per ML-KEM-768 dk key
+ * (2400 + 32 + 4608 bytes; device_bytes reports the footprint).  Nothing in it depends on the conformance mode: each call uses
+ * its context's mode for J and PRF.
+ * Import: exactly one of ek (n_keys x ek_len), dk (n_keys x dk_len) or seed (n_keys x 64, d || z) is non-NULL.  ek / dk imports
+ * run the checks of the key-validation call on ek or dk alone (FIPS 203 §7.2 modulus, §7.3 hash, in BOTH conformance modes);
+ * key_status (n_keys int32, or NULL) gets exactly the MLKEM_KEYCHECK_* bits that call writes.  If any key fails, the call returns
+ * MLKEM_ERR_KEY, leaves *out NULL and frees what it allocated.  A seed import runs KeyGen_internal (in the context's mode) into the
+ * set; key_status is then all zero.  The call runs on `stream`, uses the context's scratch and synchronises the stream.
+ * Results: for every key a set accepts, c / K are byte-identical to the per-item calls on the gathered keys
+ * (mlkem_encaps_dev on ek[key_index[i]], mlkem_decaps_dev on dk[key_index[i]]), implicit rejection included.  The one intended
+ * difference: in REFERENCE mode the per-item calls accept ek coefficients >= q (F3); a key set refuses such keys.
+ * key_index: n uint32 (device), NULL = key 0 for every item.  An index >= n_keys reads nothing outside the set: the item's c and K
+ * are written as zeros and status[i] = MLKEM_ERR_ARG (when status is given); status[i] = 0 for every other item (the checks ran at
+ * import, so there is no per-call hash status).  A set made from dk or seed serves Encaps (with the ek embedded in dk) and Decaps;
+ * a set made from ek serves Encaps only (Decaps returns MLKEM_ERR_ARG).
+ * Lifetime and threading: a set is bound to the device of the context that created it (a call through a context on another
+ * device returns MLKEM_ERR_ARG) and is read-only after creation, so any number of contexts and streams on that device may use it
+ * at once.  Destroy synchronises the set's device, zeroes every table and frees.  n == 0 is a no-op; n_keys == 0, a NULL set and
+ * misaligned pointers are MLKEM_ERR_ARG.  The key-set calls ignore the debug stage mask and always run every stage. */
+typedef struct mlkem_keyset mlkem_keyset;
+MLKEM_API int mlkem_keyset_create(mlkem_ctx* ctx, int param_set, size_t n_keys, const uint8_t* ek, const uint8_t* dk,
+                                  const uint8_t* seed, int32_t* key_status, mlkem_keyset** out, void* stream);
+MLKEM_API void mlkem_keyset_destroy(mlkem_keyset* ks);
+MLKEM_API int mlkem_keyset_info(const mlkem_keyset* ks, int* param_set, size_t* n_keys, int* has_dk, size_t* device_bytes);
+/* item i uses key key_index[i]: m : n x 32 ; c : n x c_len ; K : n x 32 ; status : n int32 or NULL */
+MLKEM_API int mlkem_encaps_keyset_dev(mlkem_ctx* ctx, const mlkem_keyset* ks, size_t n, const uint32_t* key_index,
+                                      const uint8_t* m, uint8_t* c, uint8_t* K, int32_t* status, void* stream);
+MLKEM_API int mlkem_decaps_keyset_dev(mlkem_ctx* ctx, const mlkem_keyset* ks, size_t n, const uint32_t* key_index,
+                                      const uint8_t* c, uint8_t* K, int32_t* status, void* stream);
 
 /* ---- shared-key batches, device pointers ---------------------------------------------------------------------------
  * n encapsulations to ONE encapsulation key / n decapsulations under ONE decapsulation key (a server's long-lived key):
