@@ -20,6 +20,8 @@ LIB_PATH = os.environ.get("MLKEM_LIB_PATH") or os.path.join(HERE, "libmlkem_amd.
 SHIM_PATH = os.path.join(HERE, "libml_kem.so")
 
 SIZES = {512: (800, 1632, 768), 768: (1184, 2400, 1088), 1024: (1568, 3168, 1568)}  # ek, dk, c (ml_kem.h:52-59)
+ERR_RNG = -2                # MLKEM_ERR_RNG: the OS entropy source failed
+ERR_MODULUS = -4            # per-item status of encaps in "fips203" conformance: an ek coefficient >= q
 ERR_HASH = -5
 ERR_KEY = -6                # MLKEM_ERR_KEY: a key failed validation, no key set was created (MLKEMError.key_status says which)
 ERR_ARG = -101              # MLKEM_ERR_ARG; also the per-item status of a key-set call whose key index is out of range
@@ -54,6 +56,7 @@ ABI_SYMBOLS = (
     "mlkem_decaps_seed_dev", "mlkem_decaps_seed",
     "mlkem_check_keys_dev", "mlkem_check_keys",
     "mlkem_keyset_create", "mlkem_keyset_destroy", "mlkem_keyset_info", "mlkem_encaps_keyset_dev", "mlkem_decaps_keyset_dev",
+    "mlkem_ctx_rng_seed", "mlkem_keygen_random_dev", "mlkem_encaps_random_dev", "mlkem_encaps_keyset_random_dev",
 )
 SHIM_SYMBOLS = ("init", "KEM_KeyGen", "KEM_Encaps", "KEM_Decaps", "ml_errno", "sha3_b", "sha3_h", "sha3_s", "h2b", "b2h",
                 "SampleNTT", "SamplePolyCBD", "NTT", "InverseNTT")
@@ -103,6 +106,10 @@ def load_library():
     L.mlkem_keyset_info.argtypes = [vp, C.POINTER(i32), C.POINTER(sz), C.POINTER(i32), C.POINTER(sz)]
     L.mlkem_encaps_keyset_dev.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp]
     L.mlkem_decaps_keyset_dev.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
+    L.mlkem_ctx_rng_seed.argtypes = [vp, vp]
+    L.mlkem_keygen_random_dev.argtypes = [vp, i32, sz, vp, vp, vp, vp]
+    L.mlkem_encaps_random_dev.argtypes = [vp, i32, sz, vp, vp, vp, vp, vp]
+    L.mlkem_encaps_keyset_random_dev.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
     L.mlkem_encaps_status_dev.argtypes = [vp, i32, sz, vp, vp, vp, vp, vp, vp]
     L.mlkem_ctx_set_conformance.argtypes = [vp, i32]
     L.mlkem_ctx_debug_stages.argtypes = [vp, C.c_uint]
@@ -368,6 +375,49 @@ class MLKEM:
             raise MLKEMError(rc, self.lib.mlkem_strerror(rc).decode(), key_status=status[:n])
         self._check(rc)
         return KeySet(self, h)
+
+    # -- randomised KeyGen / Encaps: seeds derived on the device (mlkem_rng.hpp) -------------------
+    def rng_seed(self, seed=None):
+        """(Re)seed the engine's generator: 32 bytes give a deterministic stream, None draws the root from the OS.  The position
+        restarts at 0.  Synchronises the device.  A random call on an engine that was never seeded seeds it from the OS itself."""
+        if seed is None:
+            self._check(self.lib.mlkem_ctx_rng_seed(self._ctx, None))
+            return
+        if isinstance(seed, self.torch.Tensor):
+            seed = seed.detach().cpu().numpy()
+        if not isinstance(seed, (bytes, bytearray)):
+            import numpy as np
+            seed = np.ascontiguousarray(seed, np.uint8).tobytes()
+        if len(seed) != 32:
+            raise MLKEMError(-101, "the generator's seed is 32 bytes")
+        buf = (C.c_uint8 * 32).from_buffer_copy(bytes(seed))
+        self._check(self.lib.mlkem_ctx_rng_seed(self._ctx, C.addressof(buf)))
+
+    def keygen_random(self, n, return_seed=False, dk=True, ek=None):
+        """ML-KEM.KeyGen() for n key pairs: d || z of item i = SHAKE256(root || 0x01 || LE64(pos + i))[:64], derived on the device.
+        -> (ek, dk), with return_seed (ek, dk, seed [n,64]); dk=False (needs return_seed) -> (ek, seed): seed-format keys for
+        decaps_seed / prepare_keys(seed=...), the expanded dk is never kept.  Not capturable (MLKEMError -101 on a capturing stream)."""
+        if not dk and not return_seed:
+            raise MLKEMError(-101, "keygen_random(dk=False) needs return_seed=True")
+        n = int(n)
+        ek = self._out(n, self.ek_len, given=ek)
+        dk_t = self._out(n, self.dk_len) if dk else None
+        seed = self._out(n, 64) if return_seed else None
+        self._check(self.lib.mlkem_keygen_random_dev(self._ctx, self.param_set, n, ek.data_ptr(), None if dk_t is None else dk_t.data_ptr(),
+                                                     None if seed is None else seed.data_ptr(), self._stream()))
+        return tuple(t for t in (ek, dk_t, seed) if t is not None)
+
+    def encaps_random(self, ek, c=None, K=None, return_status=False):
+        """ML-KEM.Encaps(ek): m of item i = SHAKE256(root || 0x02 || LE64(pos + i))[:32], derived on the device.
+        ek [n,ek_len] -> c [n,c_len], K [n,32] (+ status [n] as encaps).  Not capturable."""
+        ek = self._dev(ek, self.torch.uint8, self.ek_len)
+        n = ek.shape[0]
+        c = self._out(n, self.c_len, given=c)
+        K = self._out(n, 32, given=K)
+        st = self.torch.empty(n, dtype=self.torch.int32, device=self.device) if return_status else None
+        self._check(self.lib.mlkem_encaps_random_dev(self._ctx, self.param_set, n, ek.data_ptr(), c.data_ptr(), K.data_ptr(),
+                                                     None if st is None else st.data_ptr(), self._stream()))
+        return (c, K, st) if return_status else (c, K)
 
     # reference-style aliases
     KeyGen_internal = keygen
@@ -880,3 +930,22 @@ class KeySet:
         eng._check(self.lib.mlkem_decaps_keyset_dev(eng._ctx, self._h, n, None if idx is None else idx.data_ptr(), c.data_ptr(), K.data_ptr(),
                                                     None if st is None else st.data_ptr(), eng._stream()))
         return (K, st) if return_status else K
+
+    def encaps_random(self, n=None, key_index=None, c=None, K=None, return_status=False, engine=None):
+        """ML-KEM.Encaps to key key_index[i] for item i with m derived on the device from the engine's generator (MLKEM.rng_seed):
+        n items to key 0, or one item per entry of key_index.  Outputs and status as encaps; an out-of-range index still consumes
+        its position of the generator.  Not capturable."""
+        eng = self._engine(engine)
+        torch = eng.torch
+        if n is None:
+            if key_index is None:
+                raise MLKEMError(-101, "encaps_random needs n or key_index")
+            n = int((key_index if isinstance(key_index, torch.Tensor) else torch.as_tensor(key_index)).numel())
+        n = int(n)
+        idx = self._index(eng, key_index, n)
+        c = eng._out(n, eng.c_len, given=c)
+        K = eng._out(n, 32, given=K)
+        st = torch.empty(n, dtype=torch.int32, device=eng.device) if return_status else None
+        eng._check(self.lib.mlkem_encaps_keyset_random_dev(eng._ctx, self._h, n, None if idx is None else idx.data_ptr(), c.data_ptr(),
+                                                           K.data_ptr(), None if st is None else st.data_ptr(), eng._stream()))
+        return (c, K, st) if return_status else (c, K)

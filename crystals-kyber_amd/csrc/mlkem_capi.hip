@@ -5,6 +5,7 @@
 // linked or loaded by this library.
 #include "mlkem_pipeline.hpp"
 #include "mlkem_keyset.hpp"
+#include "mlkem_rng.hpp"
 #include "mlkem_selftest.hpp"
 
 #include "../../include/mlkem_batch.h"
@@ -73,6 +74,14 @@ struct mlkem_ctx {
     uint8_t* seed_stage = nullptr;
     size_t seed_stage_bytes = 0;
     KeysetLimits ks_lim;   // dispatch limits of the key-set calls (mlkem_keyset.hpp)
+    // generator of the randomised *_dev calls (mlkem_rng.hpp): the 32-byte root in device memory (allocated with the first use, never
+    // copied back, zeroed before it is freed), the next position (host side; 0 after every (re)seed) and the region the derived
+    // d, z / m rows of one slice pass through (chunk_items x 64 bytes, allocated with the first random call, zeroed after every call)
+    uint8_t* rng_root = nullptr;
+    bool rng_seeded = false;
+    uint64_t rng_pos = 0;
+    uint8_t* rng_seeds = nullptr;
+    size_t rng_wide_max = RNG_WIDE_ITEMS;
 };
 
 // A prepared key set (mlkem_keyset.hpp): ONE device allocation holding the keys | H(ek) | A-hat^T tables, read-only after
@@ -227,6 +236,10 @@ int mlkem_ctx_create(mlkem_ctx** out, int device, size_t chunk_items) {
         long long v = atoll(e);
         if (v >= 0) c->ks_lim.set_all((size_t)-1, (size_t)v);
     }
+    if (const char* e = getenv("MLKEM_RNG_WIDE_ITEMS")) {         // random calls up to this size derive with one sponge per wavefront (0: never)
+        long long v = atoll(e);
+        if (v >= 0) c->rng_wide_max = (size_t)v;
+    }
     // fork / join events of one-chunk calls (SideFork, mlkem_pipeline.hpp); the side stream itself comes with the first such call
     // (ctx_arm_side).  MLKEM_SIDE_STREAM=0 keeps every call on the caller's stream; failing to create the events does the same.
     const char* se = getenv("MLKEM_SIDE_STREAM");
@@ -257,6 +270,14 @@ void mlkem_ctx_destroy(mlkem_ctx* ctx) {
     if (ctx->seed_stage) {
         (void)hipMemset(ctx->seed_stage, 0, ctx->seed_stage_bytes);   // d, z and the expanded dk of the last chunk
         (void)hipFree(ctx->seed_stage);
+    }
+    if (ctx->rng_seeds) {
+        (void)hipMemset(ctx->rng_seeds, 0, ctx->ws.cap * 64);
+        (void)hipFree(ctx->rng_seeds);
+    }
+    if (ctx->rng_root) {
+        (void)hipMemset(ctx->rng_root, 0, 32);
+        (void)hipFree(ctx->rng_root);
     }
     if (ctx->scratch) {
         (void)hipMemset(ctx->scratch, 0, ctx->scratch_bytes);   // r, m', K', K-bar, PRF output: secret-dependent intermediates
@@ -1525,6 +1546,123 @@ int mlkem_encaps_random(int set, size_t n, const uint8_t* ek, unsigned ek_len, u
         explicit_bzero(m.data(), m.size());
         return rc;
     });
+}
+
+// ---- device-side seed derivation: randomised KeyGen / Encaps of device-resident batches (mlkem_rng.hpp) -------------------------
+// Without a device no context can exist: a NULL context then reports the cause, not the symptom.
+static int rng_ctx_check(const mlkem_ctx* ctx) {
+    if (!ctx) return mlkem_device_count() == 0 ? MLKEM_ERR_NO_DEVICE : MLKEM_ERR_ARG;
+    return ctx_ok(ctx) ? MLKEM_OK : MLKEM_ERR_ARG;
+}
+
+// (re)seed: the root goes up with a synchronous copy after a device synchronisation, so that the new stream starts after every
+// earlier call of the context whichever stream it ran on; the host copy is wiped by the caller
+static int rng_upload_root(mlkem_ctx* ctx, const uint8_t root[32]) {
+    if (!ctx->rng_root && !hip_ok(hipMalloc(&ctx->rng_root, 256), "hipMalloc(rng root)")) {
+        ctx->rng_root = nullptr;
+        return MLKEM_ERR_ALLOC;
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(ctx->rng_root, root, 32, hipMemcpyHostToDevice));
+    ctx->rng_seeded = true;
+    ctx->rng_pos = 0;
+    return MLKEM_OK;
+}
+
+int mlkem_ctx_rng_seed(mlkem_ctx* ctx, const uint8_t* seed) {
+    uint8_t root[32];
+    int rc = MLKEM_OK;
+    if (seed) memcpy(root, seed, 32);
+    else if (!fill_random(root, 32)) rc = MLKEM_ERR_RNG;   // the draw comes before any device work
+    if (rc == MLKEM_OK) rc = rng_ctx_check(ctx);
+    if (rc == MLKEM_OK) rc = rng_upload_root(ctx, root);
+    explicit_bzero(root, sizeof root);
+    return rc;
+}
+
+// what every random call does once its arguments are accepted and n > 0: refuse a capturing stream (a replay would repeat the
+// positions, and so the keys), seed a context that never was from the OS, and give it its derived-seed region
+static int rng_prepare(mlkem_ctx* ctx, hipStream_t st, size_t n, RngCall& g) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
+        (void)hipGetLastError();
+        return MLKEM_ERR_ARG;
+    }
+    if (!ctx->rng_seeded) {
+        const int rc = mlkem_ctx_rng_seed(ctx, nullptr);
+        if (rc) return rc;
+    }
+    if (!ctx->rng_seeds && !hip_ok(hipMalloc(&ctx->rng_seeds, ctx->ws.cap * 64), "hipMalloc(rng seeds)")) {
+        ctx->rng_seeds = nullptr;
+        return MLKEM_ERR_ALLOC;
+    }
+    g.root = ctx->rng_root;
+    g.pos = ctx->rng_pos;
+    g.seeds = ctx->rng_seeds;
+    g.slice_items = std::min(n, ctx->ws.cap);
+    g.wide_max = ctx->rng_wide_max;
+    return MLKEM_OK;
+}
+// the workspace of a sliced call: a call of several slices stays on the caller's stream, as a seeded call of that size does
+static Workspace rng_ws(mlkem_ctx* ctx, size_t n) {
+    ctx_arm_side(ctx, n);
+    Workspace ws = ctx->ws;
+    if (n > ws.cap) ws.side_on = false;
+    return ws;
+}
+
+int mlkem_keygen_random_dev(mlkem_ctx* ctx, int set, size_t n, uint8_t* ek, uint8_t* dk, uint8_t* seed_out, void* stream) {
+    ParamSet p;
+    if (!param_set(set, p)) return MLKEM_ERR_PARAM_SET;
+    if (n && (!ek || (!dk && !seed_out))) return MLKEM_ERR_ARG;
+    if (!aligned16(ek) || !aligned16(dk) || !aligned16(seed_out)) return MLKEM_ERR_ARG;
+    if (int rc = rng_ctx_check(ctx)) return rc;
+    if (n == 0) return MLKEM_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    RngCall g;
+    if (int rc = rng_prepare(ctx, st, n, g)) return rc;
+    if (!dk && !ctx_seed_stage(ctx)) return MLKEM_ERR_ALLOC;   // >= chunk_items x 4800 bytes: a slice of dk rows fits
+    ctx->rng_pos += n;
+    const int bad = keygen_random_run(st, p, n, g, ek, dk, seed_out, ctx->seed_stage, ctx->ws);
+    HIP_TRY(hipGetLastError());
+    return bad ? MLKEM_ERR_NO_DEVICE : MLKEM_OK;
+}
+
+int mlkem_encaps_random_dev(mlkem_ctx* ctx, int set, size_t n, const uint8_t* ek, uint8_t* c, uint8_t* K, int32_t* status, void* stream) {
+    ParamSet p;
+    if (!param_set(set, p)) return MLKEM_ERR_PARAM_SET;
+    if (n && (!ek || !c || !K)) return MLKEM_ERR_ARG;
+    if (!aligned16(ek) || !aligned16(c) || !aligned16(K) || (reinterpret_cast<uintptr_t>(status) & 3u)) return MLKEM_ERR_ARG;
+    if (int rc = rng_ctx_check(ctx)) return rc;
+    if (n == 0) return MLKEM_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    RngCall g;
+    if (int rc = rng_prepare(ctx, st, n, g)) return rc;
+    if (status && !ctx->ws.fips) {   // reference mode: the modulus check cannot fail (mlkem_encaps_status_dev)
+        HIP_TRY(hipMemsetAsync(status, 0, n * sizeof(int32_t), st));
+        status = nullptr;
+    }
+    ctx->rng_pos += n;
+    const Workspace ws = rng_ws(ctx, n);
+    const int bad = encaps_random_run(st, p, n, g, ek, c, K, status, ws);
+    HIP_TRY(hipGetLastError());
+    return bad ? MLKEM_ERR_NO_DEVICE : MLKEM_OK;
+}
+
+int mlkem_encaps_keyset_random_dev(mlkem_ctx* ctx, const mlkem_keyset* ks, size_t n, const uint32_t* key_index, uint8_t* c, uint8_t* K,
+                                   int32_t* status, void* stream) {
+    if (n && (!c || !K)) return MLKEM_ERR_ARG;
+    if (!aligned16(key_index) || !aligned16(c) || !aligned16(K) || (reinterpret_cast<uintptr_t>(status) & 3u)) return MLKEM_ERR_ARG;
+    if (int rc = rng_ctx_check(ctx)) return rc;
+    if (!ks || ks->device != ctx->device) return MLKEM_ERR_ARG;
+    if (n == 0) return MLKEM_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    RngCall g;
+    if (int rc = rng_prepare(ctx, st, n, g)) return rc;
+    ctx->rng_pos += n;
+    const int bad = encaps_keyset_random_run(st, ks->p, ks->v, n, g, key_index, c, K, status, ctx->ws, ctx->ks_lim);
+    HIP_TRY(hipGetLastError());
+    return bad ? MLKEM_ERR_NO_DEVICE : MLKEM_OK;
 }
 
 }   // extern "C"

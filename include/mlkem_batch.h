@@ -175,6 +175,40 @@ MLKEM_API int mlkem_encaps_keyset_dev(mlkem_ctx* ctx, const mlkem_keyset* ks, si
 MLKEM_API int mlkem_decaps_keyset_dev(mlkem_ctx* ctx, const mlkem_keyset* ks, size_t n, const uint32_t* key_index,
                                       const uint8_t* c, uint8_t* K, int32_t* status, void* stream);
 
+/* ---- randomised KeyGen / Encaps, device pointers: seeds derived on the device -----------------------------------------
+ * ML-KEM.KeyGen() and ML-KEM.Encaps(ek) (FIPS 203 algorithms 19, 20) for device-resident batches.  The context owns a generator:
+ * a 32-byte root in DEVICE memory (allocated with the first use, never copied back to the host, zeroed and freed with the context)
+ * and a 64-bit position on the host that starts at 0 after every (re)seed.  Item randomness is
+ *   block(root, dom, pos) = SHAKE256(root[32] || dom[1] || LE64(pos))     (41-byte message, one permutation)
+ *   KeyGen item:  d || z = first 64 bytes of block(root, 0x01, pos)
+ *   Encaps item:  m      = first 32 bytes of block(root, 0x02, pos)
+ * A call of n items uses positions pos .. pos + n - 1 and then sets pos += n, whatever its domain: calls of 5 and 3 items produce
+ * exactly the items of one call of 8.  Given the derived seeds every output is byte-identical to the seeded calls
+ * (mlkem_keygen_dev, mlkem_encaps_status_dev, mlkem_encaps_keyset_dev) in the context's conformance mode; the derivation itself
+ * does not depend on the mode.  d, z and m never exist in host memory or on the bus: they pass through a region of
+ * chunk_items x 64 bytes the context allocates with its first random call (larger calls are sliced) and zeroes in stream order
+ * before the call returns control of it.  This is a SHAKE256 expansion of the root, not an SP 800-90A DRBG; reseeding is explicit.
+ * STREAM CAPTURE: a captured call would replay the same positions and so the same keys; the random calls return MLKEM_ERR_ARG
+ * (and launch nothing) when `stream` is capturing.
+ * n == 0 is a no-op that leaves the position unchanged.  Without any HIP device a NULL context is MLKEM_ERR_NO_DEVICE.
+ *
+ * mlkem_ctx_rng_seed: seed != NULL gives a deterministic stream (tests, reproducible key generation, callers with their own
+ * approved RBG); seed == NULL draws the root from getrandom(2) (MLKEM_ERR_RNG on failure; the draw comes first).  A random call on a
+ * context that was never seeded seeds it from the OS first, with the same error.  The host copy of the root is wiped after the
+ * upload.  Ordering: the call SYNCHRONISES THE DEVICE and then copies synchronously, so the new stream starts after all earlier
+ * work of the context, whichever stream it was queued on. */
+MLKEM_API int mlkem_ctx_rng_seed(mlkem_ctx* ctx, const uint8_t* seed);
+/* ek : n x ek_len ; dk : n x dk_len or NULL ; seed_out : n x 64 (d || z, the seed format of mlkem_decaps_seed_dev) or NULL.
+ * dk may be NULL only when seed_out is given: the call then returns ek plus seed-format keys; the expanded dk of every slice goes
+ * through the staging region of mlkem_decaps_seed_dev, which is zeroed afterwards as it is there. */
+MLKEM_API int mlkem_keygen_random_dev(mlkem_ctx* ctx, int param_set, size_t n, uint8_t* ek, uint8_t* dk, uint8_t* seed_out, void* stream);
+/* status (n int32, or NULL) as mlkem_encaps_status_dev */
+MLKEM_API int mlkem_encaps_random_dev(mlkem_ctx* ctx, int param_set, size_t n, const uint8_t* ek, uint8_t* c, uint8_t* K, int32_t* status,
+                                      void* stream);
+/* key_index and status as mlkem_encaps_keyset_dev: an out-of-range index zeroes the item and still consumes its position */
+MLKEM_API int mlkem_encaps_keyset_random_dev(mlkem_ctx* ctx, const mlkem_keyset* ks, size_t n, const uint32_t* key_index, uint8_t* c,
+                                             uint8_t* K, int32_t* status, void* stream);
+
 /* ---- shared-key batches, device pointers ---------------------------------------------------------------------------
  * n encapsulations to ONE encapsulation key / n decapsulations under ONE decapsulation key (a server's long-lived key):
  * the same bytes as mlkem_encaps_dev / mlkem_decaps_dev on n replicated keys, but H(ek), the dk hash check and the
