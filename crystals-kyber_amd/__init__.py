@@ -57,7 +57,27 @@ ABI_SYMBOLS = (
     "mlkem_check_keys_dev", "mlkem_check_keys",
     "mlkem_keyset_create", "mlkem_keyset_destroy", "mlkem_keyset_info", "mlkem_encaps_keyset_dev", "mlkem_decaps_keyset_dev",
     "mlkem_ctx_rng_seed", "mlkem_keygen_random_dev", "mlkem_encaps_random_dev", "mlkem_encaps_keyset_random_dev",
+    "mlkem_sha3_ragged_dev", "mlkem_sha3_ragged", "mlkem_sha3_ragged_wide_max",
 )
+# MLKEM.sha3 / mlkem_sha3_ragged[_dev]: name -> (alg code MLKEM_SHA3_224 .. MLKEM_SHAKE256, rate in bytes, digest bytes; 0 = any outlen)
+SHA3_ALGS = {"sha3_224": (0, 144, 28), "sha3_256": (1, 136, 32), "sha3_384": (2, 104, 48), "sha3_512": (3, 72, 64),
+             "shake128": (4, 168, 0), "shake256": (5, 136, 0)}
+
+
+def pack_messages(msgs):
+    """Host helper of MLKEM.sha3: a list of bytes-like objects (bytes, numpy / torch uint8 arrays) -> (buffer uint8, offsets uint64,
+    lengths uint32) as numpy arrays, the messages back to back with NO alignment padding."""
+    import numpy as np
+    raw = []
+    for m in msgs:
+        if hasattr(m, "detach"):                       # a torch tensor, wherever it lives
+            m = m.detach().cpu().contiguous().numpy()
+        raw.append(m.tobytes() if hasattr(m, "tobytes") else bytes(m))
+    lens = np.array([len(r) for r in raw], np.uint32)
+    offs = np.zeros(len(raw), np.uint64)
+    if len(raw) > 1:
+        offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+    return np.frombuffer(b"".join(raw), np.uint8).copy(), offs, lens
 SHIM_SYMBOLS = ("init", "KEM_KeyGen", "KEM_Encaps", "KEM_Decaps", "ml_errno", "sha3_b", "sha3_h", "sha3_s", "h2b", "b2h",
                 "SampleNTT", "SamplePolyCBD", "NTT", "InverseNTT")
 
@@ -137,6 +157,10 @@ def load_library():
     L.mlkem_timing_end.argtypes = [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int), i32]
     L.mlkem_keccak_sponge_dev.argtypes = [vp, C.c_uint, sz, vp, C.c_uint, vp, C.c_uint, sz, vp]
     L.mlkem_keccak_sponge.argtypes = [C.c_uint, sz, vp, C.c_uint, vp, C.c_uint]
+    L.mlkem_sha3_ragged_dev.argtypes = [vp, i32, sz, vp, C.c_uint, sz, vp, sz, vp, vp, vp, C.c_uint, sz, vp, vp]
+    L.mlkem_sha3_ragged.argtypes = [i32, sz, vp, C.c_uint, sz, vp, sz, vp, vp, vp, C.c_uint, sz, vp]
+    L.mlkem_sha3_ragged_wide_max.argtypes = [vp]
+    L.mlkem_sha3_ragged_wide_max.restype = sz
     L.mlkem_sha3_pad_bits.argtypes = [vp, sz, i32, C.c_uint, vp, sz]
     L.mlkem_cells_to_bytes_dev.argtypes = [vp, sz, vp, vp, vp]
     L.mlkem_bytes_to_cells_dev.argtypes = [vp, sz, vp, vp, vp]
@@ -634,6 +658,64 @@ class MLKEM:
     def J(self, msgs):
         """J (ml_kem.c:540; SHAKE128 in the reference) -> [n,32]."""
         return self._hash(2, msgs, 32)
+
+    @property
+    def sha3_wide_max(self):
+        """calls of MLKEM.sha3 with at most this many messages run one sponge per wavefront (env MLKEM_SHA3_WIDE_ITEMS; default 4096)"""
+        return self.lib.mlkem_sha3_ragged_wide_max(self._ctx)
+
+    def sha3(self, alg, body, body_off=None, body_len=None, *, head=None, outlen=None, return_status=False):
+        """SHA-3 / SHAKE of n messages of unequal length, all on the device: message i = head[i] || body_i (mlkem_sha3_ragged_dev).
+        alg: "sha3_224" | "sha3_256" | "sha3_384" | "sha3_512" | "shake128" | "shake256" (the SHAKEs need `outlen`, 1..65536).
+        body: a list of bytes / uint8 arrays, packed back to back without padding into one device buffer; or ONE uint8 device tensor
+        used in place with `body_off` (n x int64 / uint64) and `body_len` (n x int32 / uint32): offsets in any order, overlapping or
+        repeated, lengths of 0 allowed.  head: [n, head_len] uint8 device tensor, head_len % 8 == 0, rows 8-byte aligned; a view with a
+        row stride is passed on as it is (e.g. the K of encaps_random: no copy).  -> [n, outlen] uint8 (+ status [n] int32 with
+        return_status: MLKEM_ERR_ARG and a zero row for an item whose body lies outside `body`)."""
+        torch = self.torch
+        if alg not in SHA3_ALGS:
+            raise MLKEMError(ERR_ARG, f"unknown SHA-3 algorithm {alg!r}")
+        code, _, digest = SHA3_ALGS[alg]
+        if outlen is None:
+            outlen = digest
+        outlen = int(outlen)
+        if (digest and outlen != digest) or not 1 <= outlen <= 65536:
+            raise MLKEMError(ERR_ARG, f"{alg}: outlen must be {digest or '1..65536'}")
+        if isinstance(body, (list, tuple)):
+            if body_off is not None or body_len is not None:
+                raise MLKEMError(ERR_ARG, "a list of messages carries its own offsets and lengths")
+            buf, offs, lens = pack_messages(body)
+            body = torch.from_numpy(buf).to(self.device)
+            body_off = torch.from_numpy(offs.view("int64")).to(self.device)
+            body_len = torch.from_numpy(lens.view("int32")).to(self.device)
+        else:
+            if not isinstance(body, torch.Tensor) or body.dtype != torch.uint8 or body.device != self.device or not body.is_contiguous():
+                raise MLKEMError(ERR_ARG, f"body must be a list or a contiguous uint8 tensor on {self.device}")
+            if body_off is None or body_len is None:
+                raise MLKEMError(ERR_ARG, "a body tensor needs body_off and body_len")
+            body_off = torch.as_tensor(body_off)
+            body_len = torch.as_tensor(body_len)
+            if body_off.dtype not in (torch.int64, torch.uint64) or body_len.dtype not in (torch.int32, torch.uint32):
+                raise MLKEMError(ERR_ARG, "body_off must be 64-bit and body_len 32-bit integers")
+            body_off = body_off.to(self.device).contiguous()
+            body_len = body_len.to(self.device).contiguous()
+        n = body_off.numel()
+        if body_len.numel() != n:
+            raise MLKEMError(ERR_ARG, "body_off and body_len differ in length")
+        head_ptr, head_len, head_stride = None, 0, 0
+        if head is not None:
+            if (not isinstance(head, torch.Tensor) or head.dtype != torch.uint8 or head.device != self.device or head.dim() != 2
+                    or head.shape[0] != n or (head.shape[1] > 1 and head.stride(1) != 1)):
+                raise MLKEMError(ERR_ARG, f"head must be a [n, head_len] uint8 tensor on {self.device} with contiguous rows")
+            head_ptr, head_len, head_stride = head.data_ptr(), head.shape[1], head.stride(0)
+        stride = (outlen + 3) // 4 * 4
+        out = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
+        st = torch.empty(n, dtype=torch.int32, device=self.device) if return_status else None
+        self._check(self.lib.mlkem_sha3_ragged_dev(self._ctx, code, n, head_ptr, head_len, head_stride, body.data_ptr() or None, body.numel(),
+                                                   body_off.data_ptr(), body_len.data_ptr(), out.data_ptr(), outlen, stride,
+                                                   None if st is None else st.data_ptr(), self._stream()))
+        out = out[:, :outlen]
+        return (out, st) if return_status else out
 
     def cells_to_bytes(self, cells):
         """`union byte` cells (int32 storage, value in bits 0-7) -> packed uint8, on the device."""

@@ -82,6 +82,8 @@ struct mlkem_ctx {
     uint64_t rng_pos = 0;
     uint8_t* rng_seeds = nullptr;
     size_t rng_wide_max = RNG_WIDE_ITEMS;
+    // mlkem_sha3_ragged_dev: calls of at most this many messages run one sponge per wavefront (mlkem_sha3r.hpp)
+    size_t sha3r_wide_max = SHA3R_WIDE_ITEMS;
 };
 
 // A prepared key set (mlkem_keyset.hpp): ONE device allocation holding the keys | H(ek) | A-hat^T tables, read-only after
@@ -239,6 +241,10 @@ int mlkem_ctx_create(mlkem_ctx** out, int device, size_t chunk_items) {
     if (const char* e = getenv("MLKEM_RNG_WIDE_ITEMS")) {         // random calls up to this size derive with one sponge per wavefront (0: never)
         long long v = atoll(e);
         if (v >= 0) c->rng_wide_max = (size_t)v;
+    }
+    if (const char* e = getenv("MLKEM_SHA3_WIDE_ITEMS")) {        // mlkem_sha3_ragged_dev calls up to this size: one sponge per wavefront (0: never)
+        long long v = atoll(e);
+        if (v >= 0) c->sha3r_wide_max = (size_t)v;
     }
     // fork / join events of one-chunk calls (SideFork, mlkem_pipeline.hpp); the side stream itself comes with the first such call
     // (ctx_arm_side).  MLKEM_SIDE_STREAM=0 keeps every call on the caller's stream; failing to create the events does the same.
@@ -707,6 +713,20 @@ int mlkem_keccak_sponge_dev(mlkem_ctx* ctx, unsigned rate, size_t n, const uint8
     HIP_TRY(hipGetLastError());
     return MLKEM_OK;
 }
+
+int mlkem_sha3_ragged_dev(mlkem_ctx* ctx, int alg, size_t n, const uint8_t* head, unsigned head_len, size_t head_stride, const uint8_t* body,
+                          size_t body_bytes, const uint64_t* body_off, const uint32_t* body_len, uint8_t* out, unsigned outlen,
+                          size_t out_stride, int32_t* status, void* stream) {
+    if (!ctx_ok(ctx)) return MLKEM_ERR_ARG;
+    Sha3rArgs a{n, head, head_len, head_stride, body, body_bytes, body_off, body_len, out, outlen, out_stride, status, 0};
+    unsigned rate = 0;
+    if (!sha3r_check_args(alg, a, rate)) return MLKEM_ERR_ARG;
+    if (n == 0) return MLKEM_OK;
+    if (sha3_ragged_launch(static_cast<hipStream_t>(stream), rate, a, ctx->sha3r_wide_max)) return MLKEM_ERR_ARG;
+    HIP_TRY(hipGetLastError());
+    return MLKEM_OK;
+}
+size_t mlkem_sha3_ragged_wide_max(const mlkem_ctx* ctx) { return ctx ? ctx->sha3r_wide_max : 0; }
 
 int mlkem_cells_to_bytes_dev(mlkem_ctx* ctx, size_t n, const uint32_t* cells, uint8_t* bytes, void* stream) {
     if (!ctx_ok(ctx) || (n && (!cells || !bytes)) || !aligned16(cells) || !aligned16(bytes)) return MLKEM_ERR_ARG;
@@ -1486,6 +1506,53 @@ static int host_keccak_sponge(unsigned rate, size_t n, const uint8_t* padded, un
 }
 int mlkem_keccak_sponge(unsigned rate, size_t n, const uint8_t* padded, unsigned nblocks, uint8_t* out, unsigned outlen) {
     return guarded([&]() -> int { return host_keccak_sponge(rate, n, padded, nblocks, out, outlen); });
+}
+// mlkem_sha3_ragged_dev over host pointers: the argument rules that do not concern device addresses and the per-item length limit
+// are checked here, on the host arrays; the head rows are staged packed, the output rows with a stride of their own
+static int host_sha3_ragged(int alg, size_t n, const uint8_t* head, unsigned head_len, size_t head_stride, const uint8_t* body,
+                            size_t body_bytes, const uint64_t* body_off, const uint32_t* body_len, uint8_t* out, unsigned outlen,
+                            size_t out_stride, int32_t* status) {
+    unsigned rate = 0, digest = 0;
+    uint32_t suffix = 0;
+    if (!sha3r_alg(alg, rate, digest, suffix) || (digest ? outlen != digest : (outlen < 1 || outlen > 65536))) return MLKEM_ERR_ARG;
+    if (!head) head_len = 0;
+    if (n && (!out || !body_off || !body_len || (!body && body_bytes))) return MLKEM_ERR_ARG;
+    if (n && (head_len % 8 || head_len >= (1u << 31) || head_stride < head_len || out_stride < outlen)) return MLKEM_ERR_ARG;
+    // the offsets are validated here, on the host arrays: the 2^31 limit fails the call, an item outside the body is marked and
+    // reported per item below (the kernel applies the same rule to what it is given and reads nothing of such an item)
+    std::vector<uint8_t> oob(n, 0);
+    for (size_t i = 0; i < n; i++) {
+        if ((uint64_t)head_len + body_len[i] >= (1ull << 31)) return MLKEM_ERR_ARG;
+        oob[i] = body_off[i] > (uint64_t)body_bytes || (uint64_t)body_len[i] > (uint64_t)body_bytes - body_off[i];
+    }
+    MLKEM_HOST_PROLOGUE()
+    if (n == 0) return MLKEM_OK;
+    const size_t ostride = ((size_t)outlen + 3) & ~(size_t)3;
+    DevBuf bh, bb, boff, blen, bo;
+    if ((rc = bh.alloc(n * head_len)) || (rc = bb.alloc(body_bytes)) || (rc = boff.alloc(n * 8)) || (rc = blen.alloc(n * 4)) ||
+        (rc = bo.alloc(n * ostride)))
+        return rc;
+    if (head_len) HIP_TRY(hipMemcpy2D(bh.p, head_len, head, head_stride, head_len, n, hipMemcpyHostToDevice));
+    if (body_bytes) HIP_TRY(hipMemcpy(bb.p, body, body_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(boff.p, body_off, n * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(blen.p, body_len, n * 4, hipMemcpyHostToDevice));
+    rc = mlkem_sha3_ragged_dev(ctx, alg, n, head_len ? bh.as<uint8_t>() : nullptr, head_len, head_len, body_bytes ? bb.as<uint8_t>() : nullptr,
+                               body_bytes, boff.as<uint64_t>(), blen.as<uint32_t>(), bo.as<uint8_t>(), outlen, ostride, nullptr, nullptr);
+    if (rc) return rc;
+    std::vector<uint8_t> tmp(n * ostride);
+    HIP_TRY(hipMemcpy(tmp.data(), bo.p, n * ostride, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) {
+        if (oob[i]) memset(out + i * out_stride, 0, outlen);
+        else memcpy(out + i * out_stride, tmp.data() + i * ostride, outlen);
+        if (status) status[i] = oob[i] ? MLKEM_ERR_ARG : MLKEM_OK;
+    }
+    return MLKEM_OK;
+}
+int mlkem_sha3_ragged(int alg, size_t n, const uint8_t* head, unsigned head_len, size_t head_stride, const uint8_t* body, size_t body_bytes,
+                      const uint64_t* body_off, const uint32_t* body_len, uint8_t* out, unsigned outlen, size_t out_stride, int32_t* status) {
+    return guarded([&]() -> int {
+        return host_sha3_ragged(alg, n, head, head_len, head_stride, body, body_bytes, body_off, body_len, out, outlen, out_stride, status);
+    });
 }
 // Compress_d / Decompress_d for any d in 1..12 (ml_kem.c:83-119; d = 12 is the identity there) over n values
 int mlkem_compress(int d, size_t n, const uint16_t* x, uint16_t* y) {

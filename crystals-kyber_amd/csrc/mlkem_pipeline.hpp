@@ -19,6 +19,7 @@
 #include "mlkem_kpke2.hpp"
 #include "mlkem_wkeccak.hpp"
 #include "mlkem_small.hpp"
+#include "mlkem_sha3r.hpp"
 #include "mlkem_check.hpp"
 #include <stdlib.h>
 #ifndef MLKEM_EMU
@@ -774,6 +775,24 @@ inline int sponge_raw_launch(stream_t st, unsigned rate, size_t n, const uint8_t
     case 136: launch("k_sponge_raw", k_sponge_raw<136>, grid, WAVE, st, n, msg, nblocks, out, outlen, out_stride); break;
     case 144: launch("k_sponge_raw", k_sponge_raw<144>, grid, WAVE, st, n, msg, nblocks, out, outlen, out_stride); break;
     case 168: launch("k_sponge_raw", k_sponge_raw<168>, grid, WAVE, st, n, msg, nblocks, out, outlen, out_stride); break;
+    default: return -1;
+    }
+    return 0;
+}
+
+// SHA-3 / SHAKE over messages of unequal length (mlkem_sha3r.hpp): calls of at most `wave_max` messages run one sponge per wavefront
+inline int sha3_ragged_launch(stream_t st, unsigned rate, const Sha3rArgs& a, size_t wave_max) {
+    if (a.n <= wave_max) {
+        launch("k_sha3_ragged", k_sha3_ragged_w, a.n, WAVE, st, a, rate);
+        return 0;
+    }
+    const size_t grid = ceil_div(a.n, WAVE);
+    switch (rate) {
+    case 72: launch("k_sha3_ragged", k_sha3_ragged<72>, grid, WAVE, st, a); break;
+    case 104: launch("k_sha3_ragged", k_sha3_ragged<104>, grid, WAVE, st, a); break;
+    case 136: launch("k_sha3_ragged", k_sha3_ragged<136>, grid, WAVE, st, a); break;
+    case 144: launch("k_sha3_ragged", k_sha3_ragged<144>, grid, WAVE, st, a); break;
+    case 168: launch("k_sha3_ragged", k_sha3_ragged<168>, grid, WAVE, st, a); break;
     default: return -1;
     }
     return 0;

@@ -284,6 +284,40 @@ MLKEM_API int mlkem_hash_dev(mlkem_ctx* ctx, int kind, size_t n, const uint8_t* 
  * of at most MLKEM_WIDE_HASH_ITEMS messages, runs one sponge per wavefront.  Used by the sha3.h front-ends of the drop-in shim. */
 MLKEM_API int mlkem_keccak_sponge_dev(mlkem_ctx* ctx, unsigned rate, size_t n, const uint8_t* padded, unsigned nblocks, uint8_t* out,
                             unsigned outlen, size_t out_stride, void* stream);
+/* ---- SHA-3 / SHAKE over device-resident messages of unequal length ---------------------------------------------------
+ * Message i = head[i*head_stride .. +head_len) || body[body_off[i] .. +body_len[i]): a fixed-length per-item prefix (typically the
+ * K rows an Encaps / Decaps call has just written, or K || H(ek)) followed by a per-item context of its own length.  Padding and
+ * the domain suffix are applied on the device: nothing is copied to the host, padded there or aligned.
+ * alg: MLKEM_SHA3_224 .. MLKEM_SHAKE256.  outlen must equal the digest length for the four SHA-3 algorithms; the two SHAKEs take
+ * any outlen of 1 .. 65536.
+ * head: optional, NULL means head_len = 0.  Base and head_stride 8-byte aligned, head_len % 8 == 0, head_stride >= head_len.
+ * body: starts at ANY byte address.  body_off (n x uint64) and body_len (n x uint32) are DEVICE arrays; offsets may come in any
+ * order, overlap or repeat; a length may be 0; head_len + body_len[i] must be < 2^31.  body may be NULL when body_bytes = 0.
+ * Bounds: an item with body_off[i] + body_len[i] > body_bytes (the sum taken without wrapping at 2^64), or one that breaks the
+ * 2^31 limit, reads nothing of the body: its out row is written as zeros and status[i] = MLKEM_ERR_ARG when status (n int32, or
+ * NULL) is given; every other item gets status[i] = 0 -- the rule mlkem_encaps_keyset_dev has for an index out of range.
+ * Memory: message bytes are read with naturally aligned 8-byte loads that each hold at least one byte of the item's own head or
+ * body, so a body may end at the last byte of an allocation (and begin at its first).
+ * out: 16-byte aligned, out_stride >= outlen, out_stride % 4 == 0; bytes [outlen, out_stride) of every row are left untouched.
+ * n == 0 is a no-op.  A bad alg, a bad outlen, bad alignment, or a NULL required pointer (body_off, body_len, out; body when
+ * body_bytes > 0) with n > 0 returns MLKEM_ERR_ARG and launches nothing; so does a context on another device.
+ * The call uses none of the context's scratch and is a pure function of its inputs: unlike the random calls it may be captured.
+ * Calls of at most MLKEM_SHA3_WIDE_ITEMS messages (env; default 4096; mlkem_sha3_ragged_wide_max reads it back) run one sponge per
+ * wavefront, larger ones one sponge per SIMD lane.  The limit is the call's own, not the MLKEM_WIDE_HASH_ITEMS of
+ * mlkem_keccak_sponge_dev (2048): measured, the two forms cross between 4096 and 8192 messages of 1184 bytes and between 8192 and
+ * 16384 short ones (profiles/sha3_ragged.txt).  A wave of the lane-sliced form runs as long as its longest message, and nothing
+ * sorts or bins the batch -- callers with very skewed lengths should group messages of similar length into one call.
+ * Control flow and addresses depend on lengths and offsets only, never on message bytes: the head may be a secret. */
+#define MLKEM_SHA3_224 0   /* rate 144, 28 bytes */
+#define MLKEM_SHA3_256 1   /* rate 136, 32 */
+#define MLKEM_SHA3_384 2   /* rate 104, 48 */
+#define MLKEM_SHA3_512 3   /* rate  72, 64 */
+#define MLKEM_SHAKE128 4   /* rate 168, any outlen */
+#define MLKEM_SHAKE256 5   /* rate 136, any outlen */
+MLKEM_API int mlkem_sha3_ragged_dev(mlkem_ctx* ctx, int alg, size_t n, const uint8_t* head, unsigned head_len, size_t head_stride,
+                                    const uint8_t* body, size_t body_bytes, const uint64_t* body_off, const uint32_t* body_len,
+                                    uint8_t* out, unsigned outlen, size_t out_stride, int32_t* status, void* stream);
+MLKEM_API size_t mlkem_sha3_ragged_wide_max(const mlkem_ctx* ctx);
 /* host helper, no device work: message bits (one per byte) + suffix ("01" hash / "1111" XOF: sha3.c:408-436) + pad10*1
  * (sha3.c:226-240) -> whole rate blocks in `padded`; returns the number of blocks or a negative error */
 MLKEM_API int mlkem_sha3_pad_bits(const uint8_t* msg_bits, size_t nbits, int xof, unsigned rate, uint8_t* padded, size_t padded_cap);
@@ -320,6 +354,12 @@ MLKEM_API int mlkem_sample_ntt(size_t n, const uint8_t* seeds34, uint16_t* a_hat
 MLKEM_API int mlkem_sample_ntt_retries(size_t n, const uint8_t* seeds34, uint16_t* a_hat, uint8_t* retries);
 MLKEM_API int mlkem_sample_cbd(int eta, size_t n, const uint8_t* bytes, uint16_t* f);
 MLKEM_API int mlkem_keccak_sponge(unsigned rate, size_t n, const uint8_t* padded, unsigned nblocks, uint8_t* out, unsigned outlen);
+/* mlkem_sha3_ragged_dev over host pointers: stage, run, synchronise.  Every array is a host array and no pointer needs any
+ * alignment (out_stride >= outlen is all an out row needs).  The offsets are validated on the host arrays before anything is
+ * staged: the 2^31 limit fails the call with MLKEM_ERR_ARG, an out-of-bounds item gets its zero row and status as above. */
+MLKEM_API int mlkem_sha3_ragged(int alg, size_t n, const uint8_t* head, unsigned head_len, size_t head_stride, const uint8_t* body,
+                                size_t body_bytes, const uint64_t* body_off, const uint32_t* body_len, uint8_t* out, unsigned outlen,
+                                size_t out_stride, int32_t* status);
 /* Compress / Decompress (ml_kem.c:83-119) over n host values, any d in 1..12 (reference test Test_Archive/CompressDecompress_test04.c) */
 MLKEM_API int mlkem_compress(int d, size_t n, const uint16_t* x, uint16_t* y);
 MLKEM_API int mlkem_decompress(int d, size_t n, const uint16_t* y, uint16_t* x);
