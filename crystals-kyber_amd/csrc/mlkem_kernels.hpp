@@ -390,21 +390,20 @@ __global__ void __launch_bounds__(256) k_seed_split(size_t n, const uint4* __res
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_hash_decaps — KEM_Decaps hash check (ml_kem.c:1336-1350) and Decaps_internal's hashing
-// (ml_kem.c:1187-1202): status = (H(dk.ek) == dk.h) ? 0 : -5 ; (K', r') = G(m' || dk.h) ; Kbar = J(dk.z || c)
-// J is SHAKE128 in the reference (F2): JRATE = 168; the FIPS 203 mode uses SHAKE256: JRATE = 136.
-// The three sponges of an item are independent.  With HASH_CHECK the grid holds TWO waves per 64 items: blocks [0, nb) run
-// H(ek) (9 permutations for k = 3), blocks [nb, 2 nb) run J and G (7 + 1) -- the same permutations in all, but a chain of 9
-// instead of 17 per lane: below ~2^16 items the GPU is not full and the kernel's time is the length of that chain
-// (0.174 -> 0.10 ms at 64..16384 items), at 2^20 it is neutral (profiles/r03_batch_sweep.txt).
+// k_hash_decaps — KEM_Decaps hash check (ml_kem.c:1336-1350) and Decaps_internal's G (ml_kem.c:1187-1196):
+// status = (H(dk.ek) == dk.h) ? 0 : -5 ; (K', r') = G(m' || dk.h).  Kbar = J(dk.z || c) (ml_kem.c:1198-1202) is NOT computed
+// here: K-bar is used only when the re-encryption differs from c, so the compare kernel (CMP_DEFER, mlkem_kpke2.hpp) lists the
+// rejected items and k_hash_j_rejected below hashes those alone -- 7 of this kernel's former 17 permutations per ML-KEM-768
+// item, and the read of every c, are gone from a call whose ciphertexts are accepted.
+// The sponges of an item are independent.  With HASH_CHECK the grid holds TWO waves per 64 items: blocks [0, nb) run H(ek)
+// (9 permutations for k = 3), blocks [nb, 2 nb) run G (1).
 // ------------------------------------------------------------------------------------------------
-template <int K, int CLEN, bool HASH_CHECK, int JRATE = 168>
-__global__ void __launch_bounds__(WAVE, MLKEM_KECCAK_MINWAVES) k_hash_decaps(size_t n, const uint8_t* __restrict__ dk, const uint8_t* __restrict__ c,
-                                                      const uint8_t* __restrict__ m_ws, uint8_t* __restrict__ Kp_ws,
-                                                      uint8_t* __restrict__ r_ws, uint8_t* __restrict__ Kbar_ws,
-                                                      int32_t* __restrict__ status, size_t dk_stride) {
+template <int K, bool HASH_CHECK>
+__global__ void __launch_bounds__(WAVE, MLKEM_KECCAK_MINWAVES) k_hash_decaps(size_t n, const uint8_t* __restrict__ dk, const uint8_t* __restrict__ m_ws,
+                                                      uint8_t* __restrict__ Kp_ws, uint8_t* __restrict__ r_ws, int32_t* __restrict__ status,
+                                                      size_t dk_stride) {
     // dk_stride: bytes between the decapsulation keys of consecutive items (768k+96), or 0 for a shared-key batch
-    __shared__ __attribute__((aligned(16))) uint2 stage[STAGE_QWORDS];
+    __shared__ __attribute__((aligned(16))) uint2 stage[HASH_CHECK ? stage_qwords(136) : 1];
     constexpr unsigned EK = 384 * K + 32;
     const size_t DK = dk_stride;
     const size_t nb = (n + WAVE - 1) / WAVE;
@@ -431,16 +430,6 @@ __global__ void __launch_bounds__(WAVE, MLKEM_KECCAK_MINWAVES) k_hash_decaps(siz
         if (i2 < n && status) status[i2] = diff ? -5 : 0;
         return;
     }
-    // Kbar = J(z || c)
-    {
-        MsgView mv{dk + 768 * K + 64, DK, 32, c, CLEN, CLEN};
-        wave_sponge_absorb<JRATE, 0x1F>(s, stage, mv, item0, n);
-        const size_t i2 = item0 + (size_t)lane_id_fresh();
-        if (i2 < n) {
-            MLKEM_STATE_WORDS8(s, 0, w)
-            store32(Kbar_ws, 32, i2, w);
-        }
-    }
     // (K', r') = G(m' || h)
     uint32_t mm[8];
     const size_t it = my_item();
@@ -454,6 +443,99 @@ __global__ void __launch_bounds__(WAVE, MLKEM_KECCAK_MINWAVES) k_hash_decaps(siz
         MLKEM_STATE_WORDS8(s, 8, w)
         store32(r_ws, 32, item, w);
         if (!HASH_CHECK && status) status[item] = 0;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_hash_j_rejected — Kbar = J(z || c) (ml_kem.c:1198-1202) for the items of one h-chunk whose re-encryption differed, written
+// straight into their K rows (which the compare kernel left at zero).  J is SHAKE128 in the reference (F2): JRATE = 168; the
+// FIPS 203 mode uses SHAKE256: JRATE = 136.
+// list[0] = number of entries, list[REJ_HDR + j] = index of a rejected item within the h-chunk (appended by encrypt2_body in
+// CMP_DEFER mode, in any order; the counter is zeroed in stream order before the h-chunk's first compare kernel).
+// Lane = list entry; the grid is bounded and strides over the count, and a wave beyond it returns at once: with no rejected
+// ciphertext (the normal call) the launch is all this costs.
+// z of item i: z + i * z_stride (z_stride = 0: one shared key) when n_keys = 0; otherwise the key-set form,
+// z + keyset_key(idx, n_keys, i) * z_stride.  c and Kout: rows of the h-chunk.
+// The rows are not contiguous, so there is no LDS staging: a lane reads its own message with aligned 8-byte loads, J_GROUP of
+// them issued ahead of their XORs (as k_sha3_ragged, mlkem_sha3r.hpp; z rows, c rows and the head length 32 are all 8-byte
+// aligned, so no funnel shift).  The entry is re-read and the row addresses recomputed from a fresh lane id for every rate
+// block: only the 50 state registers live across a permutation.  No secret touches LDS here, so there is nothing to zero.
+// ------------------------------------------------------------------------------------------------
+constexpr int REJ_HDR = 4;   // dwords in front of the reject list's entries (the counter first): 16 bytes
+constexpr int CMP_NONE = 0, CMP_BLEND = 1, CMP_DEFER = 2;   // encrypt2_body's compare modes (mlkem_kpke2.hpp)
+constexpr int J_GROUP = 8;   // qword loads a lane has in flight
+
+// the item's key in a prepared key set (mlkem_keyset.hpp): idx[item] (0 when idx is null); an index >= n_keys reads key 0, never
+// outside the set (k_keyset_fix / the small kernels then zero the item's outputs)
+__device__ __forceinline__ size_t keyset_key(const uint32_t* __restrict__ idx, size_t n_keys, size_t item) {
+    if (!idx) return 0;
+    const size_t k = idx[item];
+    return k < n_keys ? k : 0;
+}
+
+template <int CLEN, int JRATE>
+__global__ void __launch_bounds__(WAVE, MLKEM_KECCAK_MINWAVES) k_hash_j_rejected(const uint32_t* __restrict__ list, size_t hn,
+                                                                                 const uint8_t* __restrict__ z, size_t z_stride,
+                                                                                 const uint32_t* __restrict__ idx, size_t n_keys,
+                                                                                 const uint8_t* __restrict__ c, uint8_t* __restrict__ Kout) {
+    constexpr int NQ = JRATE / 8;
+    constexpr unsigned TOTAL = 32u + (unsigned)CLEN, NFULL = TOTAL / (unsigned)JRATE, REM = TOTAL % (unsigned)JRATE;
+    static_assert(CLEN % 8 == 0 && JRATE % 8 == 0, "qword absorb");
+    // h-chunk indices are 32-bit (as the list's entries): 32-bit arithmetic keeps the bounds in SGPRs
+    const uint32_t hn32 = (uint32_t)hn, cnt = list[0] < hn32 ? list[0] : hn32;
+    for (uint32_t base = blockIdx.x * (uint32_t)WAVE; base < cnt; base += gridDim.x * (uint32_t)WAVE) {
+        // the lane's entry (lanes past the count redo the last one and store nothing); an entry is an index below hn
+        auto my_item = [&]() {
+            const uint32_t slot = base + (uint32_t)lane_id_fresh();
+            const uint32_t it = list[REJ_HDR + (slot < cnt - 1u ? slot : cnt - 1u)];
+            return (size_t)(it < hn32 - 1u ? it : hn32 - 1u);
+        };
+        KeccakState s;
+        keccak_zero(s);
+#pragma unroll 1
+        for (unsigned b = 0; b <= NFULL; b++) {
+            const unsigned pos0 = b * (unsigned)JRATE;           // message position of the block: wave-uniform
+            const size_t it = my_item();
+            // the bases stay in SGPRs: left alone, the compiler keeps per-lane copies of them across the permutation and spills them
+            const uint8_t *zb = z, *cbase = c;
+#ifndef MLKEM_EMU
+            asm volatile("" : "+s"(zb), "+s"(cbase));
+#endif
+            const uint8_t* zr = zb + (n_keys ? keyset_key(idx, n_keys, it) : it) * z_stride;
+            // qword w of the block is message position pos0 + 8 w: byte 8 w - 32 behind cb in the c row -- except the four qwords
+            // of z, which are qwords 0 .. 3 of block 0 (a wave-uniform select of the address: ONE load per qword)
+            const uint8_t* cb = cbase + it * (size_t)CLEN + pos0;
+#pragma unroll
+            for (int w0 = 0; w0 < NQ; w0 += J_GROUP) {
+                uint2 raw[J_GROUP];
+#pragma unroll
+                for (int k = 0; k < J_GROUP; k++) {
+                    const int w = w0 + k;
+                    raw[k].x = 0; raw[k].y = 0;
+                    const uint8_t* src = cb + (8 * w - 32);
+                    if (w < 4) src = b == 0 ? zr + 8 * w : src;
+                    if (w < NQ && pos0 + 8u * (unsigned)w < TOTAL) raw[k] = *reinterpret_cast<const uint2*>(src);
+                }
+#pragma unroll
+                for (int k = 0; k < J_GROUP; k++) {
+                    if (w0 + k >= NQ) break;
+                    s.lo[w0 + k] ^= raw[k].x;
+                    s.hi[w0 + k] ^= raw[k].y;
+                }
+                pin_state<NQ>(s);
+                sched_fence();
+            }
+            const bool last = b == NFULL;                        // pad10*1 in the (partial) last block
+            keccak_xor_byte<REM>(s, last ? 0x1Fu : 0u);
+            keccak_xor_byte<JRATE - 1>(s, last ? 0x80u : 0u);
+            keccak_f1600(s);
+        }
+        const uint32_t slot = base + (uint32_t)lane_id_fresh();
+        if (slot < cnt) {
+            uint32_t w[8];
+            MLKEM_STATE_WORDS8(s, 0, w)
+            store32(Kout, 32, my_item(), w);
+        }
     }
 }
 

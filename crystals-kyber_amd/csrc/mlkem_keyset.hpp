@@ -3,7 +3,7 @@
 // A key set holds, per key, the bytes of ek or dk, h = H(ek) and A-hat^T (k x k polynomials, uint16, the layout the sampler writes
 // with transpose = 1).  The FIPS 203 §7.2 / §7.3 input checks run once, at import; later calls name each item's key by index and
 // run none of the key's work again: per ML-KEM-768 item 8 of Encaps' 44 Keccak-f remain (G + 7 PRF rows) and 15 of Decaps' 51
-// (G + J + 7 PRF rows).
+// (G + J + 7 PRF rows; in the batch form J runs for rejected ciphertexts only: 8 for an accepted one).
 //
 // Import (keyset_import_run): the check kernel of mlkem_check_keys_dev on the set's own copy of the keys, k_hash_batch<0> for the
 // H table, the sampler (n_xof = keys of a chunk, transpose = 1) writing straight into the set's A-hat^T table; the status words
@@ -13,7 +13,8 @@
 //   small calls (KeysetLimits)     k_encaps_keyset_small / k_decaps_keyset_small: one launch, one workgroup per item (as the
 //                                  kernels of mlkem_small.hpp, minus H(ek), the hash check and the k^2 SampleNTT jobs)
 //   larger                         the batch pipeline with indexed kernels: k_hash_g_keyset, the PRF rows of the sampler,
-//                                  k_encrypt2_keyset; k_decrypt4_keyset, k_keyset_gather32 (z), k_hash_decaps_keyset; then
+//                                  k_encrypt2_keyset; k_decrypt4_keyset, k_hash_decaps_keyset (G alone), the compare in CMP_DEFER
+//                                  mode and k_hash_j_rejected (J(z || c) of the rejected items, z read from the set by index); then
 //                                  k_keyset_fix writes the status words and zeroes the outputs of items whose index is out of range
 // Every gathering kernel bounds-checks its index (keyset_key): an index >= n_keys reads key 0, never outside the set.
 #pragma once
@@ -37,7 +38,8 @@ struct KeysetView {
 // Calls of at most enc_max_k[k - 2] (Encaps) / dec_max_k[k - 2] (Decaps) items run one workgroup per item; of those, calls of at
 // most enc_lat_k / dec_lat_k items use eight waves per item, larger ones four.  The values are where the forms cross in the sweep of
 // tools/keyset_sweep.py on one MI355X (sizes 1 .. 4096; LABNOTES "Prepared key sets"): Decaps keeps the small kernels about twice
-// as far as Encaps because its batch path runs J lane-sliced (7-9 chained permutations at 8.8 us).  Env MLKEM_KEYSET_SMALL_ITEMS /
+// as far as Encaps because its batch path ran J lane-sliced for every item when they were swept (7-9 chained permutations at
+// 8.8 us; it now defers J to the rejected items, and the Decaps limits have not been swept again).  Env MLKEM_KEYSET_SMALL_ITEMS /
 // MLKEM_KEYSET_LATENCY_ITEMS set all of them.
 struct KeysetLimits {
     size_t enc_max_k[3] = {1536, 1024, 768}, dec_max_k[3] = {3072, 2048, 3072};
@@ -54,13 +56,7 @@ struct KeysetLimits {
     }
 };
 
-// the item's key: idx[item] (0 when idx is null); an index >= n_keys reads key 0 (k_keyset_fix / the small kernels then zero
-// the item's outputs)
-__device__ __forceinline__ size_t keyset_key(const uint32_t* __restrict__ idx, size_t n_keys, size_t item) {
-    if (!idx) return 0;
-    const size_t k = idx[item];
-    return k < n_keys ? k : 0;
-}
+// keyset_key (the item's key, bounds-checked) lives in mlkem_kernels.hpp: k_hash_j_rejected resolves z rows with it
 
 // ------------------------------------------------------------------------------------------------
 // Batch path
@@ -84,70 +80,48 @@ __global__ void __launch_bounds__(WAVE, MLKEM_KECCAK_MINWAVES) k_hash_g_keyset(s
     }
 }
 
-// 32-byte rows src[key * stride ..] of every item's key -> dst[item * 32 ..] (one dword per thread)
-__global__ void __launch_bounds__(256) k_keyset_gather32(size_t n, const uint32_t* __restrict__ idx, size_t n_keys, const uint8_t* __restrict__ src,
-                                                         size_t stride, uint32_t* __restrict__ dst) {
-    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= 8 * n) return;
-    const size_t item = g >> 3;
-    dst[g] = reinterpret_cast<const uint32_t*>(src + keyset_key(idx, n_keys, item) * stride)[g & 7];
-}
-
-// Decaps_internal's hashing (ml_kem.c:1187-1202) with the key's z and h: Kbar = J(z || c) from the gathered z rows (z_ws, 32 bytes
-// per item, zeroed here after use) through the staged sponge of k_hash_decaps; (K', r') = G(m' || h[key])
-template <int K, int CLEN, int JRATE>
+// Decaps_internal's G (ml_kem.c:1187-1196) with the key's h: (K', r') = G(m' || h[key]).  J(z || c) is deferred to the rejected items
+// (k_hash_j_rejected reads z from the set by index): no z row is gathered into scratch any more.  zero_ws: the item's 32-byte row of
+// the scratch region that earlier versions gathered z into (ws.rho); it is still written to zero, so that "no key material is left in
+// the context scratch after a key-set Decaps" stays a property the CPU tier reads back from that region.
 __global__ void __launch_bounds__(WAVE, MLKEM_KECCAK_MINWAVES) k_hash_decaps_keyset(size_t n, const uint32_t* __restrict__ idx, size_t n_keys,
-                                                                                    const uint8_t* __restrict__ hs, uint8_t* __restrict__ z_ws,
-                                                                                    const uint8_t* __restrict__ c, const uint8_t* __restrict__ m_ws,
-                                                                                    uint8_t* __restrict__ Kp_ws, uint8_t* __restrict__ r_ws,
-                                                                                    uint8_t* __restrict__ Kbar_ws) {
-    __shared__ __attribute__((aligned(16))) uint2 stage[STAGE_QWORDS];
-    const size_t item0 = (size_t)blockIdx.x * WAVE;
-    KeccakState s;
-    uint32_t h[8], w[8];
-    {
-        MsgView mv{z_ws, 32, 32, c, CLEN, CLEN};
-        wave_sponge_absorb<JRATE, 0x1F>(s, stage, mv, item0, n);
-        const size_t i2 = item0 + (size_t)lane_id_fresh();
-        if (i2 < n) {
-            MLKEM_STATE_WORDS8(s, 0, w)
-            store32(Kbar_ws, 32, i2, w);
-            // z is a long-term secret: the gathered row goes back to zero once the sponge has absorbed it (only this wave reads the
-            // rows of its items, and every one of its loads has landed before the final permutation)
-            uint32_t* zr = reinterpret_cast<uint32_t*>(z_ws + i2 * 32);
-#pragma unroll
-            for (int q = 0; q < 8; q++) zr[q] = 0u;
-        }
-    }
-    uint32_t mm[8];
-    const size_t i3 = item0 + (size_t)lane_id_fresh(), it = i3 < n ? i3 : n - 1;
+                                                                                    const uint8_t* __restrict__ hs, uint8_t* __restrict__ zero_ws,
+                                                                                    const uint8_t* __restrict__ m_ws, uint8_t* __restrict__ Kp_ws,
+                                                                                    uint8_t* __restrict__ r_ws) {
+    const size_t item = (size_t)blockIdx.x * WAVE + lane_id();
+    const size_t it = item < n ? item : n - 1;
+    uint32_t mm[8], hh[8], w[8];
     load32(m_ws, 32, it, mm);
-    load32(hs, 32, keyset_key(idx, n_keys, it), h);
-    lane_G64(s, mm, h);
-    const size_t item = item0 + (size_t)lane_id_fresh();
+    load32(hs, 32, keyset_key(idx, n_keys, it), hh);
+    KeccakState s;
+    lane_G64(s, mm, hh);
     if (item < n) {
         MLKEM_STATE_WORDS8(s, 0, w)
         store32(Kp_ws, 32, item, w);
         MLKEM_STATE_WORDS8(s, 8, w)
         store32(r_ws, 32, item, w);
+#pragma unroll
+        for (int q = 0; q < 8; q++) w[q] = 0u;
+        store32(zero_ws, 32, item, w);
     }
 }
 
 // K-PKE.Encrypt two items per wave (encrypt2_body) with ek and A-hat^T of each half-wave's key: the two items of a wave may have
 // different keys, so the key rows are per-lane pointers (stride 0 inside the body), 64-bit offsets into the set
-template <int K, int ETA1, int DU, int DV, bool COMPARE>
+template <int K, int ETA1, int DU, int DV, int CMP>
 __global__ void __launch_bounds__(WAVE * KPKE2_WAVES, kpke2_minwaves(K))
 k_encrypt2_keyset(size_t n, const uint32_t* __restrict__ idx, size_t n_keys, const uint8_t* __restrict__ ek, size_t ek_stride,
                   const uint16_t* __restrict__ At, const uint8_t* __restrict__ msg, const uint8_t* __restrict__ prf, uint8_t* __restrict__ c_out,
-                  const uint8_t* __restrict__ c_in, const uint8_t* __restrict__ Kp, const uint8_t* __restrict__ Kbar, uint8_t* __restrict__ Kout) {
+                  const uint8_t* __restrict__ c_in, const uint8_t* __restrict__ Kp, uint8_t* __restrict__ Kout, uint32_t* __restrict__ rej,
+                  uint32_t rej_base) {
     __shared__ K2Lds<K + 1> lds_all[KPKE2_WAVES];
     const int wv = wave_id();
     const size_t item0 = 2 * ((size_t)blockIdx.x * KPKE2_WAVES + wv);
     if (item0 >= n) return;
     const size_t h = (size_t)(lane_id() >> 5), item = item0 + h < n ? item0 + h : item0;   // the body's item of this half
     const size_t key = keyset_key(idx, n_keys, item);
-    encrypt2_body<K, ETA1, DU, DV, COMPARE>(lds_all[wv].xch, item0, n, ek + key * ek_stride, 0, msg, At + key * (size_t)(K * K * 256), prf,
-                                            c_out, c_in, Kp, Kbar, Kout, (int32_t*)nullptr, 0);
+    encrypt2_body<K, ETA1, DU, DV, CMP>(lds_all[wv].xch, item0, n, ek + key * ek_stride, 0, msg, At + key * (size_t)(K * K * 256), prf,
+                                        c_out, c_in, Kp, (const uint8_t*)nullptr, Kout, (int32_t*)nullptr, 0, rej, rej_base);
 }
 
 // K-PKE.Decrypt four items per wave (decrypt4_body) with dk_pke of each item's key
@@ -387,9 +361,9 @@ inline void encaps_keyset_run(stream_t st, const ParamSet& p, const KeysetView& 
         for (size_t c0 = 0; c0 < hn; c0 += ws.cap) {
             const size_t cn = min_sz(ws.cap, hn - c0), i0 = h0 + c0;
             launch_sample_split(st, p, 0, cn, nullptr, 0, 1, ws.r + c0 * 32, 2 * K + 1, K, ws);   // PRF rows per item
-            launch("k_encrypt_keyset", k_encrypt2_keyset<K, ETA1, DU, DV, false>, ceil_div(ceil_div(cn, 2), KPKE2_WAVES), WAVE * KPKE2_WAVES, st, cn,
+            launch("k_encrypt_keyset", k_encrypt2_keyset<K, ETA1, DU, DV, CMP_NONE>, ceil_div(ceil_div(cn, 2), KPKE2_WAVES), WAVE * KPKE2_WAVES, st, cn,
                    idx ? idx + i0 : nullptr, ks.n_keys, ek, ks.key_stride, ks.At, m + i0 * 32, (const uint8_t*)ws.prf, c + i0 * p.c_len,
-                   (const uint8_t*)nullptr, (const uint8_t*)nullptr, (const uint8_t*)nullptr, (uint8_t*)nullptr);
+                   (const uint8_t*)nullptr, (const uint8_t*)nullptr, (uint8_t*)nullptr, (uint32_t*)nullptr, 0u);
         }
     }
     if (idx || status)
@@ -418,23 +392,19 @@ inline void decaps_keyset_run(stream_t st, const ParamSet& p, const KeysetView& 
         const uint8_t* ch = c + h0 * p.c_len;
         launch("k_decrypt_keyset", k_decrypt4_keyset<K, DU, DV>, ceil_div(ceil_div(hn, 4), KPKE4_WAVES), 64 * KPKE4_WAVES, st, hn, idh, ks.n_keys,
                ks.keys, ks.key_stride, ch, ws.m);
-        // z of every item's key into ws.rho (unused by Decaps otherwise), the row layout the staged J sponge reads
-        launch("k_keyset_gather32", k_keyset_gather32, ceil_div(8 * hn, 256), 256u, st, hn, idh, ks.n_keys, ks.keys + 768 * K + 64, ks.key_stride,
-               reinterpret_cast<uint32_t*>(ws.rho));
-        if (!ws.fips)
-            launch("k_hash_decaps_keyset", k_hash_decaps_keyset<K, CLEN, 168>, ceil_div(hn, WAVE), WAVE, st, hn, idh, ks.n_keys, ks.h,
-                   ws.rho, ch, (const uint8_t*)ws.m, ws.Kp, ws.r, ws.Kbar);
-        else
-            launch("k_hash_decaps_keyset", k_hash_decaps_keyset<K, CLEN, 136>, ceil_div(hn, WAVE), WAVE, st, hn, idh, ks.n_keys, ks.h,
-                   ws.rho, ch, (const uint8_t*)ws.m, ws.Kp, ws.r, ws.Kbar);
+        reject_list_reset(st, ws);
+        launch("k_hash_decaps_keyset", k_hash_decaps_keyset, ceil_div(hn, WAVE), WAVE, st, hn, idh, ks.n_keys, ks.h, ws.rho, (const uint8_t*)ws.m,
+               ws.Kp, ws.r);
         for (size_t c0 = 0; c0 < hn; c0 += ws.cap) {
             const size_t cn = min_sz(ws.cap, hn - c0), i0 = h0 + c0;
             launch_sample_split(st, p, 0, cn, nullptr, 0, 1, ws.r + c0 * 32, 2 * K + 1, K, ws);
-            launch("k_encrypt_cmp_keyset", k_encrypt2_keyset<K, ETA1, DU, DV, true>, ceil_div(ceil_div(cn, 2), KPKE2_WAVES), WAVE * KPKE2_WAVES, st,
-                   cn, idx ? idx + i0 : nullptr, ks.n_keys, ks.keys + 384 * K, ks.key_stride, ks.At, (const uint8_t*)(ws.m + c0 * 32),
-                   (const uint8_t*)ws.prf, (uint8_t*)nullptr, c + i0 * p.c_len, (const uint8_t*)(ws.Kp + c0 * 32), (const uint8_t*)(ws.Kbar + c0 * 32),
-                   Kout + i0 * 32);
+            launch("k_encrypt_cmp_keyset", k_encrypt2_keyset<K, ETA1, DU, DV, CMP_DEFER>, ceil_div(ceil_div(cn, 2), KPKE2_WAVES), WAVE * KPKE2_WAVES,
+                   st, cn, idx ? idx + i0 : nullptr, ks.n_keys, ks.keys + 384 * K, ks.key_stride, ks.At, (const uint8_t*)(ws.m + c0 * 32),
+                   (const uint8_t*)ws.prf, (uint8_t*)nullptr, c + i0 * p.c_len, (const uint8_t*)(ws.Kp + c0 * 32), Kout + i0 * 32, reject_list(ws),
+                   (uint32_t)c0);
         }
+        // J(z || c) of the rejected items, z from the set by index -- before k_keyset_fix, which zeroes the K rows of bad indices
+        j_rejected_launch<CLEN>(st, ws, hn, ks.keys + 768 * K + 64, ks.key_stride, idh, ks.n_keys, ch, Kout + h0 * 32);
     }
     if (idx || status)
         launch("k_keyset_fix", k_keyset_fix, min_sz(ceil_div(n, 256), 1024), 256u, st, n, idx, ks.n_keys, (uint8_t*)nullptr, p.c_len, Kout, status);

@@ -495,19 +495,25 @@ __device__ __forceinline__ uint32_t k2_emit(const v2f (&p)[4], int t, uint8_t* o
 
 // ------------------------------------------------------------------------------------------------
 // k_encrypt2 / encrypt2_body — K-PKE.Encrypt (ml_kem.c:776-936) for two items per wave, given A^T and the PRF bytes of the sampler.
-//   COMPARE = false : write c                                   (Encaps_internal, ml_kem.c:1127)
-//   COMPARE = true  : compare c' with c, K = (c == c') ? K' : Kbar (Decaps_internal, ml_kem.c:1206-1215)
+//   CMP = CMP_NONE  : write c                                   (Encaps_internal, ml_kem.c:1127)
+//   CMP = CMP_BLEND : compare c' with c, K = (c == c') ? K' : Kbar (Decaps_internal, ml_kem.c:1206-1215); Kbar = J(z || c) of every
+//                     item was computed before (the one-sponge-per-wavefront hash kernels of mid-size calls)
+//   CMP = CMP_DEFER : compare c' with c, K = (c == c') ? K' : 0, and the h-chunk index of every rejected item is appended to the
+//                     reject list `rej` (rej[0] = count, entries from rej[REJ_HDR]); k_hash_j_rejected (mlkem_kernels.hpp) then
+//                     writes Kbar = J(z || c) into the K rows of the listed items alone.  Kbar is not read.
 // ek: packed keys, ek_stride bytes apart (0: one shared key) ; A: matrices, a_stride uint16 apart (0: one shared matrix) ;
 // prf: (2K+1) rows of PS bytes per item ; mod_status (may be null): -4 where a t-hat coefficient is >= q (FIPS 203 mode).
 // ------------------------------------------------------------------------------------------------
 // encrypt2_body: the work of ONE wave -- items item0 and item0 + 1 of the n the pointers describe; `xch` = the wave's exchange
 // buffers (K2Lds<K + 1>::xch).  Called by k_encrypt2 (batches) and by the one-workgroup-per-item kernels of mlkem_small.hpp.
-template <int K, int ETA1, int DU, int DV, bool COMPARE>
+// rej / rej_base (CMP_DEFER): the reject list of the h-chunk and the h-chunk index of the item the pointers' item 0 is
+template <int K, int ETA1, int DU, int DV, int CMP>
 __device__ __forceinline__ void
 encrypt2_body(float2 (*xch)[2][128], size_t item0, size_t n, const uint8_t* __restrict__ ek, size_t ek_stride, const uint8_t* __restrict__ msg,
               const uint16_t* __restrict__ A, const uint8_t* __restrict__ prf, uint8_t* __restrict__ c_out, const uint8_t* __restrict__ c_in,
               const uint8_t* __restrict__ Kp, const uint8_t* __restrict__ Kbar, uint8_t* __restrict__ Kout, int32_t* __restrict__ mod_status,
-              size_t a_stride) {
+              size_t a_stride, uint32_t* __restrict__ rej = nullptr, uint32_t rej_base = 0) {
+    constexpr bool COMPARE = CMP != CMP_NONE;
     const int l = lane_id(), h = l >> 5, t = l & 31, nb = k2_blk(t);   // nb: the lane's block of 8 coefficients in NAT layout
     const bool valid = item0 + (size_t)h < n;          // n odd: the upper half of the last wave redoes item n - 1, stores nothing
     const unsigned hh = valid ? (unsigned)h : 0u;      // the half's item = item0 + hh; per-lane offsets are 32-bit
@@ -617,7 +623,7 @@ encrypt2_body(float2 (*xch)[2][128], size_t item0, size_t n, const uint8_t* __re
         const bool bad = ((bal >> (32 * h)) & 0xFFFFFFFFull) != 0;
         if (t == 0 && valid) mod_status[item] = bad ? -4 : 0;
     }
-    if constexpr (COMPARE) {
+    if constexpr (CMP == CMP_BLEND) {
         // both candidates are read and blended by mask: neither a branch nor an address depends on whether the ciphertext
         // matched (ml_kem.c:1206-1215 exits at the first mismatch; implicit rejection is meant to hide it)
         const unsigned long long bal = __ballot(diff != 0);
@@ -626,6 +632,23 @@ encrypt2_body(float2 (*xch)[2][128], size_t item0, size_t n, const uint8_t* __re
             const uint32_t kp = reinterpret_cast<const uint32_t*>(Kp + item * 32)[t];
             const uint32_t kb = reinterpret_cast<const uint32_t*>(Kbar + item * 32)[t];
             reinterpret_cast<uint32_t*>(Kout + item * 32)[t] = (kp & ~reject) | (kb & reject);
+        }
+    }
+    if constexpr (CMP == CMP_DEFER) {
+        // The compare is the one above: OR over every differing word, so nothing depends on WHERE or HOW MUCH c' differs.  What
+        // does depend on the outcome from here on is the accept / reject bit alone, which whoever made the ciphertext knows
+        // ("Timing"): a rejected item costs one list entry here and its J(z || c) in k_hash_j_rejected.
+        // K' of a rejected item is masked to zero BEFORE the store: it is a function of m' and never reaches caller memory.
+        const unsigned long long bal = __ballot(diff != 0);
+        const uint32_t reject = ((bal >> (32 * h)) & 0xFFFFFFFFull) != 0 ? 0xFFFFFFFFu : 0u;
+        if (t < 8 && valid) {
+            const uint32_t kp = reinterpret_cast<const uint32_t*>(Kp + item * 32)[t];
+            reinterpret_cast<uint32_t*>(Kout + item * 32)[t] = kp & ~reject;
+        }
+        // one atomic and one store under the half-wave's lane-0 mask, outside every loop
+        if (t == 0 && valid && reject) {
+            const uint32_t j = atomicAdd(&rej[0], 1u);
+            rej[REJ_HDR + j] = rej_base + (uint32_t)item;
         }
     }
 }
@@ -760,16 +783,18 @@ encrypt1_body(float2 (*xch)[2][128], const uint8_t* __restrict__ ek, const uint8
     }
 }
 
-template <int K, int ETA1, int DU, int DV, bool COMPARE>
+template <int K, int ETA1, int DU, int DV, int CMP>
 __global__ void __launch_bounds__(WAVE * KPKE2_WAVES, kpke2_minwaves(K))
 k_encrypt2(size_t n, const uint8_t* __restrict__ ek, size_t ek_stride, const uint8_t* __restrict__ msg, const uint16_t* __restrict__ A,
            const uint8_t* __restrict__ prf, uint8_t* __restrict__ c_out, const uint8_t* __restrict__ c_in, const uint8_t* __restrict__ Kp,
-           const uint8_t* __restrict__ Kbar, uint8_t* __restrict__ Kout, int32_t* __restrict__ mod_status, size_t a_stride) {
+           const uint8_t* __restrict__ Kbar, uint8_t* __restrict__ Kout, int32_t* __restrict__ mod_status, size_t a_stride,
+           uint32_t* __restrict__ rej, uint32_t rej_base) {
     __shared__ K2Lds<K + 1> lds_all[KPKE2_WAVES];   // K forward, then K + 1 inverse transforms in flight
     const int wv = wave_id();
     const size_t item0 = 2 * ((size_t)blockIdx.x * KPKE2_WAVES + wv);     // wave-uniform: item bases live in SGPRs
     if (item0 >= n) return;
-    encrypt2_body<K, ETA1, DU, DV, COMPARE>(lds_all[wv].xch, item0, n, ek, ek_stride, msg, A, prf, c_out, c_in, Kp, Kbar, Kout, mod_status, a_stride);
+    encrypt2_body<K, ETA1, DU, DV, CMP>(lds_all[wv].xch, item0, n, ek, ek_stride, msg, A, prf, c_out, c_in, Kp, Kbar, Kout, mod_status, a_stride,
+                                        rej, rej_base);
 }
 
 // canonical representatives in [0, q) of the lane's pairs (any |x| <= 2^24), as integers

@@ -105,7 +105,8 @@ inline bool param_set(int set, ParamSet& p) {
 //   leftover 4*(k*k)   sponge indices needing a restart from the seed (+2 counter words)
 //   resume   208*(k*k)/8   saved sponges (index, count, Keccak state) that need a 4th squeeze block: room for 1/8 of all
 //                      sponges (expected: 0.8 %), the overflow goes to the restart list
-// Per h-chunk item: r, rho, m, Kp, Kbar : 32 bytes each.
+// Per h-chunk item: r, rho, m, Kp, Kbar : 32 bytes each.  Kbar holds K-bar rows in mid-size calls and the reject list of the
+// h-chunk (reject_list below) in the calls that defer J.
 struct Workspace {
     uint16_t* A = nullptr;      // sampled matrices of one chunk
     uint8_t *prf = nullptr, *r = nullptr, *rho = nullptr, *m = nullptr, *Kp = nullptr, *Kbar = nullptr;
@@ -240,9 +241,29 @@ inline void launch_sample(stream_t st, const ParamSet& p, size_t n, const uint8_
 }
 
 // K-PKE.Encrypt launch: two items per wave (mlkem_kpke2.hpp)
-template <int K, int ETA1, int DU, int DV, bool CMP, class... Args>
+template <int K, int ETA1, int DU, int DV, int CMP, class... Args>
 inline void encrypt_launch(const char* label, stream_t st, size_t n, Args... args) {
     launch(label, k_encrypt2<K, ETA1, DU, DV, CMP>, ceil_div(ceil_div(n, 2), KPKE2_WAVES), WAVE * KPKE2_WAVES, st, n, args...);
+}
+
+// Deferred implicit rejection (Decaps calls above ws.wide_kem(K) items, shared-key and key-set batches): the compare kernels of an
+// h-chunk run in CMP_DEFER mode and list the rejected items, then ONE k_hash_j_rejected launch computes J(z || c) for the listed
+// items.  The list lives in the ws.Kbar region, which these paths no longer use for K-bar: a 16-byte header (the counter first) and
+// 4 bytes per h-chunk item fit its 32 bytes per item for any hcap >= 1.
+inline uint32_t* reject_list(const Workspace& ws) { return reinterpret_cast<uint32_t*>(ws.Kbar); }
+// before the h-chunk's first compare kernel, in stream order (whatever ws.stages selects: the compare kernels append)
+inline void reject_list_reset(stream_t st, const Workspace& ws) { zero_u32x2(st, reject_list(ws)); }
+// after its last one.  z / z_stride / idx / n_keys as k_hash_j_rejected; ch, Kh: the c and K rows of the h-chunk
+template <int CLEN>
+inline void j_rejected_launch(stream_t st, const Workspace& ws, size_t hn, const uint8_t* z, size_t z_stride, const uint32_t* idx, size_t n_keys,
+                              const uint8_t* ch, uint8_t* Kh) {
+    if (!(ws.stages & 1u)) return;
+    // one lane per entry; 2048 waves (two per SIMD) stride over a longer list.  An empty list costs the launch alone.
+    const size_t grid = min_sz(ceil_div(hn, WAVE), 2048);
+    if (!ws.fips)
+        launch("k_hash_j_rejected", k_hash_j_rejected<CLEN, 168>, grid, WAVE, st, (const uint32_t*)reject_list(ws), hn, z, z_stride, idx, n_keys, ch, Kh);
+    else
+        launch("k_hash_j_rejected", k_hash_j_rejected<CLEN, 136>, grid, WAVE, st, (const uint32_t*)reject_list(ws), hn, z, z_stride, idx, n_keys, ch, Kh);
 }
 
 // ---- ML-KEM.KeyGen_internal (ml_kem.c:1034-1084) ; z == nullptr: K-PKE.KeyGen alone (ml_kem.c:651-769, dk = 384k-byte ŝ) ----
@@ -318,9 +339,9 @@ inline void encaps_run(stream_t st, const ParamSet& p, size_t n, const uint8_t* 
                 launch_sample(st, p, cn, eki + 384 * K, p.ek_len, /*transpose=*/1, r_h + c0 * 32, 2 * K + 1, K, ws);
             }
             if (ws.stages & 4u)
-            encrypt_launch<K, ETA1, DU, DV, false>("k_encrypt", st, cn, eki, (size_t)p.ek_len, m + i0 * 32, (const uint16_t*)ws.A, (const uint8_t*)ws.prf,
+            encrypt_launch<K, ETA1, DU, DV, CMP_NONE>("k_encrypt", st, cn, eki, (size_t)p.ek_len, m + i0 * 32, (const uint16_t*)ws.A, (const uint8_t*)ws.prf,
                    c + i0 * p.c_len, (const uint8_t*)nullptr, (const uint8_t*)nullptr, (const uint8_t*)nullptr, (uint8_t*)nullptr,
-                   mod_status ? mod_status + i0 : (int32_t*)nullptr, (size_t)(K * K * 256));
+                   mod_status ? mod_status + i0 : (int32_t*)nullptr, (size_t)(K * K * 256), (uint32_t*)nullptr, 0u);
         }
     }
 }
@@ -361,8 +382,13 @@ inline void decaps_run(stream_t st, const ParamSet& p, size_t n, const uint8_t* 
         if (ws.stages & 8u) decrypt_launch<K, DU, DV>(st, hn, dkh, (size_t)p.dk_len, ch, ws.m);
         int32_t* sth = (hash_check && status) ? status + h0 : (int32_t*)nullptr;
         const size_t hgrid = ceil_div(hn, WAVE);
+        // Mid-size calls (one sponge per wavefront) keep the blend: there J runs on its own waves beside the longer H(ek) chain and
+        // is not what the call waits for -- one more launch on the chain would be.  Above ws.wide_kem(K) the call is throughput
+        // bound, every permutation counts, and J is deferred to the rejected items.
+        const bool wide = n <= ws.wide_kem(K);
+        if (!wide) reject_list_reset(st, ws);
         if (!(ws.stages & 1u)) {
-        } else if (n <= ws.wide_kem(K)) {   // small call: one sponge per wave (mlkem_wkeccak.hpp)
+        } else if (wide) {   // one sponge per wave (mlkem_wkeccak.hpp)
             if (hash_check && !ws.fips)
                 launch("k_hash_decaps", k_hash_decaps_w<K, CLEN, true, 168>, 2 * hn, WAVE, st, hn, dkh, ch, (const uint8_t*)ws.m, ws.Kp, ws.r, ws.Kbar, sth, (size_t)p.dk_len);
             else if (!ws.fips)
@@ -371,15 +397,10 @@ inline void decaps_run(stream_t st, const ParamSet& p, size_t n, const uint8_t* 
                 launch("k_hash_decaps", k_hash_decaps_w<K, CLEN, true, 136>, 2 * hn, WAVE, st, hn, dkh, ch, (const uint8_t*)ws.m, ws.Kp, ws.r, ws.Kbar, sth, (size_t)p.dk_len);
             else
                 launch("k_hash_decaps", k_hash_decaps_w<K, CLEN, false, 136>, hn, WAVE, st, hn, dkh, ch, (const uint8_t*)ws.m, ws.Kp, ws.r, ws.Kbar, sth, (size_t)p.dk_len);
-        } else
-        if (hash_check && !ws.fips)
-            launch("k_hash_decaps", k_hash_decaps<K, CLEN, true, 168>, 2 * hgrid, WAVE, st, hn, dkh, ch, (const uint8_t*)ws.m, ws.Kp, ws.r, ws.Kbar, sth, (size_t)p.dk_len);
-        else if (!ws.fips)
-            launch("k_hash_decaps", k_hash_decaps<K, CLEN, false, 168>, hgrid, WAVE, st, hn, dkh, ch, (const uint8_t*)ws.m, ws.Kp, ws.r, ws.Kbar, sth, (size_t)p.dk_len);
-        else if (hash_check)
-            launch("k_hash_decaps", k_hash_decaps<K, CLEN, true, 136>, 2 * hgrid, WAVE, st, hn, dkh, ch, (const uint8_t*)ws.m, ws.Kp, ws.r, ws.Kbar, sth, (size_t)p.dk_len);
+        } else if (hash_check)
+            launch("k_hash_decaps", k_hash_decaps<K, true>, 2 * hgrid, WAVE, st, hn, dkh, (const uint8_t*)ws.m, ws.Kp, ws.r, sth, (size_t)p.dk_len);
         else
-            launch("k_hash_decaps", k_hash_decaps<K, CLEN, false, 136>, hgrid, WAVE, st, hn, dkh, ch, (const uint8_t*)ws.m, ws.Kp, ws.r, ws.Kbar, sth, (size_t)p.dk_len);
+            launch("k_hash_decaps", k_hash_decaps<K, false>, hgrid, WAVE, st, hn, dkh, (const uint8_t*)ws.m, ws.Kp, ws.r, sth, (size_t)p.dk_len);
         for (size_t c0 = 0; c0 < hn; c0 += ws.cap) {
             const size_t cn = min_sz(ws.cap, hn - c0), i0 = h0 + c0;
             const uint8_t* dki = dk + i0 * p.dk_len;
@@ -389,11 +410,17 @@ inline void decaps_run(stream_t st, const ParamSet& p, size_t n, const uint8_t* 
             } else if (ws.stages & 2u) {
                 launch_sample(st, p, cn, dki + 768 * K, p.dk_len, /*transpose=*/1, ws.r + c0 * 32, 2 * K + 1, K, ws);
             }
-            if (ws.stages & 4u)
-            encrypt_launch<K, ETA1, DU, DV, true>("k_encrypt_cmp", st, cn, dki + 384 * K, (size_t)p.dk_len, (const uint8_t*)(ws.m + c0 * 32), (const uint16_t*)ws.A,
-                   (const uint8_t*)ws.prf, (uint8_t*)nullptr, c + i0 * p.c_len, (const uint8_t*)(ws.Kp + c0 * 32),
-                   (const uint8_t*)(ws.Kbar + c0 * 32), Kout + i0 * 32, (int32_t*)nullptr, (size_t)(K * K * 256));
+            if (!(ws.stages & 4u)) continue;
+            if (wide)
+                encrypt_launch<K, ETA1, DU, DV, CMP_BLEND>("k_encrypt_cmp", st, cn, dki + 384 * K, (size_t)p.dk_len, (const uint8_t*)(ws.m + c0 * 32),
+                       (const uint16_t*)ws.A, (const uint8_t*)ws.prf, (uint8_t*)nullptr, c + i0 * p.c_len, (const uint8_t*)(ws.Kp + c0 * 32),
+                       (const uint8_t*)(ws.Kbar + c0 * 32), Kout + i0 * 32, (int32_t*)nullptr, (size_t)(K * K * 256), (uint32_t*)nullptr, 0u);
+            else
+                encrypt_launch<K, ETA1, DU, DV, CMP_DEFER>("k_encrypt_cmp", st, cn, dki + 384 * K, (size_t)p.dk_len, (const uint8_t*)(ws.m + c0 * 32),
+                       (const uint16_t*)ws.A, (const uint8_t*)ws.prf, (uint8_t*)nullptr, c + i0 * p.c_len, (const uint8_t*)(ws.Kp + c0 * 32),
+                       (const uint8_t*)nullptr, Kout + i0 * 32, (int32_t*)nullptr, (size_t)(K * K * 256), reject_list(ws), (uint32_t)c0);
         }
+        if (!wide) j_rejected_launch<CLEN>(st, ws, hn, dkh + 768 * K + 64, (size_t)p.dk_len, (const uint32_t*)nullptr, (size_t)0, ch, Kout + h0 * 32);
     }
 }
 
@@ -507,9 +534,9 @@ inline void encaps_shared_run(stream_t st, const ParamSet& p, size_t n, const ui
         for (size_t c0 = 0; c0 < hn; c0 += ws.cap) {
             const size_t cn = min_sz(ws.cap, hn - c0), i0 = h0 + c0;
             launch_sample_split(st, p, 0, cn, nullptr, 0, 1, ws.r + c0 * 32, 2 * K + 1, K, w);      // PRF rows per item
-            encrypt_launch<K, ETA1, DU, DV, false>("k_encrypt", st, cn, ek, (size_t)0,
+            encrypt_launch<K, ETA1, DU, DV, CMP_NONE>("k_encrypt", st, cn, ek, (size_t)0,
                    m + i0 * 32, (const uint16_t*)w.A, (const uint8_t*)w.prf, c + i0 * p.c_len, (const uint8_t*)nullptr,
-                   (const uint8_t*)nullptr, (const uint8_t*)nullptr, (uint8_t*)nullptr, (int32_t*)nullptr, (size_t)0);
+                   (const uint8_t*)nullptr, (const uint8_t*)nullptr, (uint8_t*)nullptr, (int32_t*)nullptr, (size_t)0, (uint32_t*)nullptr, 0u);
         }
     }
 }
@@ -528,17 +555,17 @@ inline void decaps_shared_run(stream_t st, const ParamSet& p, size_t n, const ui
         const uint8_t* ch = c + h0 * p.c_len;
         decrypt_launch<K, DU, DV>(st, hn, dk, (size_t)0, ch, ws.m);
         const size_t hgrid = ceil_div(hn, WAVE);
-        if (!ws.fips)
-            launch("k_hash_decaps", k_hash_decaps<K, CLEN, false, 168>, hgrid, WAVE, st, hn, dk, ch, (const uint8_t*)ws.m, ws.Kp, ws.r, ws.Kbar, (int32_t*)nullptr, (size_t)0);
-        else
-            launch("k_hash_decaps", k_hash_decaps<K, CLEN, false, 136>, hgrid, WAVE, st, hn, dk, ch, (const uint8_t*)ws.m, ws.Kp, ws.r, ws.Kbar, (int32_t*)nullptr, (size_t)0);
+        reject_list_reset(st, ws);
+        launch("k_hash_decaps", k_hash_decaps<K, false>, hgrid, WAVE, st, hn, dk, (const uint8_t*)ws.m, ws.Kp, ws.r, (int32_t*)nullptr, (size_t)0);
         for (size_t c0 = 0; c0 < hn; c0 += ws.cap) {
             const size_t cn = min_sz(ws.cap, hn - c0), i0 = h0 + c0;
             launch_sample_split(st, p, 0, cn, nullptr, 0, 1, ws.r + c0 * 32, 2 * K + 1, K, w);
-            encrypt_launch<K, ETA1, DU, DV, true>("k_encrypt_cmp", st, cn, dk + 384 * K,
+            encrypt_launch<K, ETA1, DU, DV, CMP_DEFER>("k_encrypt_cmp", st, cn, dk + 384 * K,
                    (size_t)0, (const uint8_t*)(ws.m + c0 * 32), (const uint16_t*)w.A, (const uint8_t*)w.prf, (uint8_t*)nullptr, c + i0 * p.c_len,
-                   (const uint8_t*)(ws.Kp + c0 * 32), (const uint8_t*)(ws.Kbar + c0 * 32), Kout + i0 * 32, (int32_t*)nullptr, (size_t)0);
+                   (const uint8_t*)(ws.Kp + c0 * 32), (const uint8_t*)nullptr, Kout + i0 * 32, (int32_t*)nullptr, (size_t)0, reject_list(ws),
+                   (uint32_t)c0);
         }
+        j_rejected_launch<CLEN>(st, ws, hn, dk + 768 * K + 64, (size_t)0, (const uint32_t*)nullptr, (size_t)0, ch, Kout + h0 * 32);
     }
 }
 inline int encaps_shared_dispatch(stream_t st, int set, size_t n, const uint8_t* ek, const uint8_t* m, uint8_t* c, uint8_t* K, const Workspace& ws) {
