@@ -58,10 +58,14 @@ ABI_SYMBOLS = (
     "mlkem_keyset_create", "mlkem_keyset_destroy", "mlkem_keyset_info", "mlkem_encaps_keyset_dev", "mlkem_decaps_keyset_dev",
     "mlkem_ctx_rng_seed", "mlkem_keygen_random_dev", "mlkem_encaps_random_dev", "mlkem_encaps_keyset_random_dev",
     "mlkem_sha3_ragged_dev", "mlkem_sha3_ragged", "mlkem_sha3_ragged_wide_max",
+    "mlkem_cshake_dev", "mlkem_kmac_dev", "mlkem_cshake", "mlkem_kmac",
 )
 # MLKEM.sha3 / mlkem_sha3_ragged[_dev]: name -> (alg code MLKEM_SHA3_224 .. MLKEM_SHAKE256, rate in bytes, digest bytes; 0 = any outlen)
 SHA3_ALGS = {"sha3_224": (0, 144, 28), "sha3_256": (1, 136, 32), "sha3_384": (2, 104, 48), "sha3_512": (3, 72, 64),
              "shake128": (4, 168, 0), "shake256": (5, 136, 0)}
+# MLKEM.kmac / mlkem_kmac[_dev]: name -> (alg code MLKEM_KMAC128 .. MLKEM_KMACXOF256, security strength in bits, rate in bytes, XOF)
+KMAC_ALGS = {"kmac128": (0, 128, 168, False), "kmac256": (1, 256, 136, False),
+             "kmacxof128": (2, 128, 168, True), "kmacxof256": (3, 256, 136, True)}
 
 
 def pack_messages(msgs):
@@ -160,6 +164,11 @@ def load_library():
     L.mlkem_sha3_ragged_dev.argtypes = [vp, i32, sz, vp, C.c_uint, sz, vp, sz, vp, vp, vp, C.c_uint, sz, vp, vp]
     L.mlkem_sha3_ragged.argtypes = [i32, sz, vp, C.c_uint, sz, vp, sz, vp, vp, vp, C.c_uint, sz, vp]
     L.mlkem_sha3_ragged_wide_max.argtypes = [vp]
+    ragged = [vp, C.c_uint, vp, C.c_uint, sz, vp, sz, vp, vp, vp, C.c_uint, sz, vp]   # lead, head, body, offsets, lengths, out, status
+    L.mlkem_cshake_dev.argtypes = [vp, i32, sz, vp, C.c_uint, vp, C.c_uint] + ragged + [vp]
+    L.mlkem_kmac_dev.argtypes = [vp, i32, sz, vp, C.c_uint, sz, vp, C.c_uint] + ragged + [vp]
+    L.mlkem_cshake.argtypes = [i32, sz, vp, C.c_uint, vp, C.c_uint] + ragged
+    L.mlkem_kmac.argtypes = [i32, sz, vp, C.c_uint, sz, vp, C.c_uint] + ragged
     L.mlkem_sha3_ragged_wide_max.restype = sz
     L.mlkem_sha3_pad_bits.argtypes = [vp, sz, i32, C.c_uint, vp, sz]
     L.mlkem_cells_to_bytes_dev.argtypes = [vp, sz, vp, vp, vp]
@@ -716,6 +725,116 @@ class MLKEM:
                                                    None if st is None else st.data_ptr(), self._stream()))
         out = out[:, :outlen]
         return (out, st) if return_status else out
+
+    def _ragged_args(self, body, body_off, body_len, head, lead, outlen):
+        """the checks and conversions MLKEM.cshake / MLKEM.kmac share with MLKEM.sha3 -> (n, body, body_off, body_len, head triple, lead)"""
+        torch = self.torch
+        if not 1 <= outlen <= 65536:
+            raise MLKEMError(ERR_ARG, "outlen must be 1..65536")
+        lead = bytes(lead)
+        if len(lead) > 8:
+            raise MLKEMError(ERR_ARG, "lead is at most 8 bytes")
+        if isinstance(body, (list, tuple)):
+            if body_off is not None or body_len is not None:
+                raise MLKEMError(ERR_ARG, "a list of messages carries its own offsets and lengths")
+            buf, offs, lens = pack_messages(body)
+            body = torch.from_numpy(buf).to(self.device)
+            body_off = torch.from_numpy(offs.view("int64")).to(self.device)
+            body_len = torch.from_numpy(lens.view("int32")).to(self.device)
+        else:
+            if not isinstance(body, torch.Tensor) or body.dtype != torch.uint8 or body.device != self.device or not body.is_contiguous():
+                raise MLKEMError(ERR_ARG, f"body must be a list or a contiguous uint8 tensor on {self.device}")
+            if body_off is None or body_len is None:
+                raise MLKEMError(ERR_ARG, "a body tensor needs body_off and body_len")
+            body_off = torch.as_tensor(body_off)
+            body_len = torch.as_tensor(body_len)
+            if body_off.dtype not in (torch.int64, torch.uint64) or body_len.dtype not in (torch.int32, torch.uint32):
+                raise MLKEMError(ERR_ARG, "body_off must be 64-bit and body_len 32-bit integers")
+            body_off = body_off.to(self.device).contiguous()
+            body_len = body_len.to(self.device).contiguous()
+        n = body_off.numel()
+        if body_len.numel() != n:
+            raise MLKEMError(ERR_ARG, "body_off and body_len differ in length")
+        hd = (None, 0, 0)
+        if head is not None:
+            if (not isinstance(head, torch.Tensor) or head.dtype != torch.uint8 or head.device != self.device or head.dim() != 2
+                    or head.shape[0] != n or (head.shape[1] > 1 and head.stride(1) != 1)):
+                raise MLKEMError(ERR_ARG, f"head must be a [n, head_len] uint8 tensor on {self.device} with contiguous rows")
+            hd = (head.data_ptr(), head.shape[1], head.stride(0))
+        return n, body, body_off, body_len, hd, lead
+
+    def _ragged_call(self, fn, front, n, body, body_off, body_len, hd, lead, outlen, return_status):
+        torch = self.torch
+        stride = (outlen + 3) // 4 * 4
+        out = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
+        st = torch.empty(n, dtype=torch.int32, device=self.device) if return_status else None
+        self._check(fn(self._ctx, *front, lead or None, len(lead), *hd, body.data_ptr() or None, body.numel(), body_off.data_ptr(),
+                       body_len.data_ptr(), out.data_ptr(), outlen, stride, None if st is None else st.data_ptr(), self._stream()))
+        out = out[:, :outlen]
+        return (out, st) if return_status else out
+
+    def cshake(self, bits, body, body_off=None, body_len=None, *, head=None, lead=b"", outlen, function_name=b"", custom=b"",
+               return_status=False):
+        """SP 800-185 cSHAKE128 / 256 (bits) of n messages of unequal length, all on the device (mlkem_cshake_dev):
+        out[i] = cSHAKE(lead || head[i] || body_i, 8 * outlen, N = function_name, S = custom); N = S = b"" is SHAKE.
+        lead: 0..8 host bytes, the same for every item.  body / body_off / body_len / head / return_status: as MLKEM.sha3.
+        function_name (<= 32 bytes) and custom (<= 256 bytes) are public host bytes."""
+        if bits not in (128, 256):
+            raise MLKEMError(ERR_ARG, "bits must be 128 or 256")
+        N, S = bytes(function_name), bytes(custom)
+        if len(N) > 32 or len(S) > 256:
+            raise MLKEMError(ERR_ARG, "function_name is at most 32 bytes and custom at most 256")
+        outlen = int(outlen)
+        n, body, body_off, body_len, hd, lead = self._ragged_args(body, body_off, body_len, head, lead, outlen)
+        return self._ragged_call(self.lib.mlkem_cshake_dev, (bits, n, N or None, len(N), S or None, len(S)), n, body, body_off, body_len, hd,
+                                 lead, outlen, return_status)
+
+    def kmac(self, bits, key, body, body_off=None, body_len=None, *, head=None, lead=b"", outlen, custom=b"", xof=False, return_status=False):
+        """SP 800-185 KMAC128 / 256 (bits; KMACXOF with xof=True) of n messages of unequal length, all on the device (mlkem_kmac_dev):
+        out[i] = KMAC(key_i, lead || head[i] || body_i, 8 * outlen, S = custom).
+        key: a [n, key_len] uint8 device tensor USED IN PLACE (key_len % 8 == 0, 8..128, rows 8-byte aligned; a view with a row stride
+        is passed on as it is, e.g. the K of encaps_random), or ONE shared key for all items: a 1-D uint8 device tensor or bytes
+        (0..512 bytes; bytes are copied to the device).  Everything else as MLKEM.cshake."""
+        torch = self.torch
+        name = ("kmacxof%d" if xof else "kmac%d") % bits if bits in (128, 256) else None
+        if name not in KMAC_ALGS:
+            raise MLKEMError(ERR_ARG, "bits must be 128 or 256")
+        S = bytes(custom)
+        if len(S) > 256:
+            raise MLKEMError(ERR_ARG, "custom is at most 256 bytes")
+        if isinstance(key, (bytes, bytearray, memoryview)):
+            if len(key) > 512:
+                raise MLKEMError(ERR_ARG, "a shared key is at most 512 bytes")
+            import numpy as np
+            key = torch.from_numpy(np.frombuffer(bytes(key), np.uint8).copy()).to(self.device)
+        if not isinstance(key, torch.Tensor) or key.dtype != torch.uint8 or key.device != self.device or key.dim() not in (1, 2):
+            raise MLKEMError(ERR_ARG, f"key must be bytes or a 1-D / 2-D uint8 tensor on {self.device}")
+        outlen = int(outlen)
+        n, body, body_off, body_len, hd, lead = self._ragged_args(body, body_off, body_len, head, lead, outlen)
+        if key.dim() == 1:
+            if key.numel() > 512 or (key.numel() > 1 and key.stride(0) != 1):
+                raise MLKEMError(ERR_ARG, "a shared key is a contiguous tensor of at most 512 bytes")
+            kd = (key.data_ptr() if key.numel() else None, key.numel(), 0)
+        else:
+            kl = key.shape[1]
+            if key.shape[0] != n or kl % 8 or not 8 <= kl <= 128 or key.stride(1) != 1 or (n > 1 and key.stride(0) < kl):
+                raise MLKEMError(ERR_ARG, "per-item keys: [n, key_len] with key_len % 8 == 0, 8..128, and contiguous rows")
+            kd = (key.data_ptr(), kl, max(key.stride(0), kl))
+        return self._ragged_call(self.lib.mlkem_kmac_dev, (KMAC_ALGS[name][0], n, *kd, S or None, len(S)), n, body, body_off, body_len, hd,
+                                 lead, outlen, return_status)
+
+    def kdf_onestep(self, Z, fixed_info, outlen, bits=256, salt=None):
+        """SP 800-56C r2 section 4.1, option 3 (H = KMAC#) with H_outputBits = L, i.e. one repetition, all on the device:
+        out[i] = KMAC#(salt, 00000001 || Z[i] || FixedInfo_i, 8 * outlen, "KDF").  Z: [n, len] uint8 device tensor used in place as the
+        head (len % 8 == 0: the K rows of encaps / decaps); fixed_info: a list of bytes or (body, body_off, body_len) as MLKEM.kmac;
+        salt: bytes or a 1-D device tensor, None = the default all-zero salt of 164 (KMAC128) / 132 (KMAC256) bytes."""
+        if bits not in (128, 256):
+            raise MLKEMError(ERR_ARG, "bits must be 128 or 256")
+        if salt is None:
+            salt = bytes(164 if bits == 128 else 132)
+        in_place = isinstance(fixed_info, tuple) and len(fixed_info) == 3 and isinstance(fixed_info[0], self.torch.Tensor)
+        body, off, ln = fixed_info if in_place else (fixed_info, None, None)
+        return self.kmac(bits, salt, body, off, ln, head=Z, lead=b"\x00\x00\x00\x01", outlen=outlen, custom=b"KDF")
 
     def cells_to_bytes(self, cells):
         """`union byte` cells (int32 storage, value in bits 0-7) -> packed uint8, on the device."""

@@ -84,6 +84,10 @@ struct mlkem_ctx {
     size_t rng_wide_max = RNG_WIDE_ITEMS;
     // mlkem_sha3_ragged_dev: calls of at most this many messages run one sponge per wavefront (mlkem_sha3r.hpp)
     size_t sha3r_wide_max = SHA3R_WIDE_ITEMS;
+    // mlkem_cshake_dev / mlkem_kmac_dev: the midstate k_kmac_prefix leaves for the per-item kernels (mlkem_kmac.hpp; KMAC_MID_BYTES).
+    // Allocated with the context, so that no call allocates (a first call may already be captured); zeroed after every shared-key
+    // call and before it is freed.
+    uint64_t* kmac_mid = nullptr;
 };
 
 // A prepared key set (mlkem_keyset.hpp): ONE device allocation holding the keys | H(ek) | A-hat^T tables, read-only after
@@ -201,6 +205,13 @@ int mlkem_ctx_create(mlkem_ctx** out, int device, size_t chunk_items) {
         delete c;
         return MLKEM_ERR_ALLOC;
     }
+    if (!hip_ok(hipMalloc(&c->kmac_mid, KMAC_MID_BYTES), "hipMalloc(kmac midstate)") ||
+        !hip_ok(hipMemset(c->kmac_mid, 0, KMAC_MID_BYTES), "hipMemset(kmac midstate)")) {
+        if (c->kmac_mid) (void)hipFree(c->kmac_mid);
+        (void)hipFree(c->scratch);
+        delete c;
+        return MLKEM_ERR_ALLOC;
+    }
     uint8_t* base = static_cast<uint8_t*>(c->scratch);
     c->ws.A = reinterpret_cast<uint16_t*>(base);
     c->ws.prf = base + szA;
@@ -284,6 +295,10 @@ void mlkem_ctx_destroy(mlkem_ctx* ctx) {
     if (ctx->rng_root) {
         (void)hipMemset(ctx->rng_root, 0, 32);
         (void)hipFree(ctx->rng_root);
+    }
+    if (ctx->kmac_mid) {
+        (void)hipMemset(ctx->kmac_mid, 0, KMAC_MID_BYTES);
+        (void)hipFree(ctx->kmac_mid);
     }
     if (ctx->scratch) {
         (void)hipMemset(ctx->scratch, 0, ctx->scratch_bytes);   // r, m', K', K-bar, PRF output: secret-dependent intermediates
@@ -727,6 +742,35 @@ int mlkem_sha3_ragged_dev(mlkem_ctx* ctx, int alg, size_t n, const uint8_t* head
     return MLKEM_OK;
 }
 size_t mlkem_sha3_ragged_wide_max(const mlkem_ctx* ctx) { return ctx ? ctx->sha3r_wide_max : 0; }
+
+// cSHAKE / KMAC over messages of unequal length (mlkem_kmac.hpp): the argument rules are kmac_check_args', the form switch is the
+// ragged SHA-3 call's own limit
+static int kmac_dev_run(mlkem_ctx* ctx, KmacCall& c, void* stream) {
+    if (!ctx_ok(ctx)) return MLKEM_ERR_ARG;
+    unsigned rate = 0;
+    if (!kmac_check_args(c, true, rate)) return MLKEM_ERR_ARG;
+    if (c.s.n == 0) return MLKEM_OK;
+    if (kmac_launch(static_cast<hipStream_t>(stream), rate, c, ctx->kmac_mid, ctx->sha3r_wide_max)) return MLKEM_ERR_ARG;
+    HIP_TRY(hipGetLastError());
+    return MLKEM_OK;
+}
+int mlkem_cshake_dev(mlkem_ctx* ctx, int bits, size_t n, const uint8_t* fname, unsigned fname_len, const uint8_t* custom, unsigned custom_len,
+                     const uint8_t* lead, unsigned lead_len, const uint8_t* head, unsigned head_len, size_t head_stride, const uint8_t* body,
+                     size_t body_bytes, const uint64_t* body_off, const uint32_t* body_len, uint8_t* out, unsigned outlen, size_t out_stride,
+                     int32_t* status, void* stream) {
+    KmacCall c{bits, false, false, fname, fname_len, custom, custom_len, lead, lead_len, nullptr, 0, 0,
+               Sha3rArgs{n, head, head_len, head_stride, body, body_bytes, body_off, body_len, out, outlen, out_stride, status, 0}};
+    return kmac_dev_run(ctx, c, stream);
+}
+int mlkem_kmac_dev(mlkem_ctx* ctx, int alg, size_t n, const uint8_t* key, unsigned key_len, size_t key_stride, const uint8_t* custom,
+                   unsigned custom_len, const uint8_t* lead, unsigned lead_len, const uint8_t* head, unsigned head_len, size_t head_stride,
+                   const uint8_t* body, size_t body_bytes, const uint64_t* body_off, const uint32_t* body_len, uint8_t* out, unsigned outlen,
+                   size_t out_stride, int32_t* status, void* stream) {
+    if (alg < MLKEM_KMAC128 || alg > MLKEM_KMACXOF256) return MLKEM_ERR_ARG;
+    KmacCall c{(alg & 1) ? 256 : 128, true, alg >= MLKEM_KMACXOF128, nullptr, 0, custom, custom_len, lead, lead_len, key, key_len, key_stride,
+               Sha3rArgs{n, head, head_len, head_stride, body, body_bytes, body_off, body_len, out, outlen, out_stride, status, 0}};
+    return kmac_dev_run(ctx, c, stream);
+}
 
 int mlkem_cells_to_bytes_dev(mlkem_ctx* ctx, size_t n, const uint32_t* cells, uint8_t* bytes, void* stream) {
     if (!ctx_ok(ctx) || (n && (!cells || !bytes)) || !aligned16(cells) || !aligned16(bytes)) return MLKEM_ERR_ARG;
@@ -1552,6 +1596,67 @@ int mlkem_sha3_ragged(int alg, size_t n, const uint8_t* head, unsigned head_len,
                       const uint64_t* body_off, const uint32_t* body_len, uint8_t* out, unsigned outlen, size_t out_stride, int32_t* status) {
     return guarded([&]() -> int {
         return host_sha3_ragged(alg, n, head, head_len, head_stride, body, body_bytes, body_off, body_len, out, outlen, out_stride, status);
+    });
+}
+// mlkem_cshake_dev / mlkem_kmac_dev over host pointers, as host_sha3_ragged: kmac_check_args' rules that do not concern device
+// addresses and the per-item length limit are checked here, on the host arrays; head and key rows are staged packed, a shared key as
+// it is, the output rows with a stride of their own
+static int host_kmac(KmacCall c) {
+    unsigned rate = 0;
+    if (!kmac_check_args(c, false, rate)) return MLKEM_ERR_ARG;
+    const Sha3rArgs h = c.s;            // the caller's host arrays
+    const size_t n = h.n;
+    std::vector<uint8_t> oob(n, 0);
+    for (size_t i = 0; i < n; i++) {
+        if ((uint64_t)c.lead_len + h.head_len + h.body_len[i] >= (1ull << 31)) return MLKEM_ERR_ARG;
+        oob[i] = h.body_off[i] > (uint64_t)h.body_bytes || (uint64_t)h.body_len[i] > (uint64_t)h.body_bytes - h.body_off[i];
+    }
+    MLKEM_HOST_PROLOGUE()
+    if (n == 0) return MLKEM_OK;
+    const size_t ostride = ((size_t)h.outlen + 3) & ~(size_t)3;
+    const bool per_item = c.kmac && c.key_stride;
+    const size_t key_bytes = c.kmac ? (per_item ? n * c.key_len : c.key_len) : 0;
+    DevBuf bh, bb, boff, blen, bo, bk;
+    if ((rc = bh.alloc(n * h.head_len)) || (rc = bb.alloc(h.body_bytes)) || (rc = boff.alloc(n * 8)) || (rc = blen.alloc(n * 4)) ||
+        (rc = bo.alloc(n * ostride)) || (rc = bk.alloc(key_bytes)))
+        return rc;
+    if (h.head_len) HIP_TRY(hipMemcpy2D(bh.p, h.head_len, h.head, h.head_stride, h.head_len, n, hipMemcpyHostToDevice));
+    if (h.body_bytes) HIP_TRY(hipMemcpy(bb.p, h.body, h.body_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(boff.p, h.body_off, n * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(blen.p, h.body_len, n * 4, hipMemcpyHostToDevice));
+    if (per_item) HIP_TRY(hipMemcpy2D(bk.p, c.key_len, c.key, c.key_stride, c.key_len, n, hipMemcpyHostToDevice));
+    else if (key_bytes) HIP_TRY(hipMemcpy(bk.p, c.key, key_bytes, hipMemcpyHostToDevice));
+    c.key = key_bytes ? bk.as<uint8_t>() : nullptr;
+    if (per_item) c.key_stride = c.key_len;
+    c.s = Sha3rArgs{n, h.head_len ? bh.as<uint8_t>() : nullptr, h.head_len, h.head_len, h.body_bytes ? bb.as<uint8_t>() : nullptr, h.body_bytes,
+                    boff.as<uint64_t>(), blen.as<uint32_t>(), bo.as<uint8_t>(), h.outlen, ostride, nullptr, 0};
+    if ((rc = kmac_dev_run(ctx, c, nullptr))) return rc;
+    std::vector<uint8_t> tmp(n * ostride);
+    HIP_TRY(hipMemcpy(tmp.data(), bo.p, n * ostride, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) {
+        if (oob[i]) memset(h.out + i * h.out_stride, 0, h.outlen);
+        else memcpy(h.out + i * h.out_stride, tmp.data() + i * ostride, h.outlen);
+        if (h.status) h.status[i] = oob[i] ? MLKEM_ERR_ARG : MLKEM_OK;
+    }
+    return MLKEM_OK;
+}
+int mlkem_cshake(int bits, size_t n, const uint8_t* fname, unsigned fname_len, const uint8_t* custom, unsigned custom_len, const uint8_t* lead,
+                 unsigned lead_len, const uint8_t* head, unsigned head_len, size_t head_stride, const uint8_t* body, size_t body_bytes,
+                 const uint64_t* body_off, const uint32_t* body_len, uint8_t* out, unsigned outlen, size_t out_stride, int32_t* status) {
+    return guarded([&]() -> int {
+        return host_kmac(KmacCall{bits, false, false, fname, fname_len, custom, custom_len, lead, lead_len, nullptr, 0, 0,
+                                  Sha3rArgs{n, head, head_len, head_stride, body, body_bytes, body_off, body_len, out, outlen, out_stride, status, 0}});
+    });
+}
+int mlkem_kmac(int alg, size_t n, const uint8_t* key, unsigned key_len, size_t key_stride, const uint8_t* custom, unsigned custom_len,
+               const uint8_t* lead, unsigned lead_len, const uint8_t* head, unsigned head_len, size_t head_stride, const uint8_t* body,
+               size_t body_bytes, const uint64_t* body_off, const uint32_t* body_len, uint8_t* out, unsigned outlen, size_t out_stride,
+               int32_t* status) {
+    if (alg < MLKEM_KMAC128 || alg > MLKEM_KMACXOF256) return MLKEM_ERR_ARG;
+    return guarded([&]() -> int {
+        return host_kmac(KmacCall{(alg & 1) ? 256 : 128, true, alg >= MLKEM_KMACXOF128, nullptr, 0, custom, custom_len, lead, lead_len, key,
+                                  key_len, key_stride,
+                                  Sha3rArgs{n, head, head_len, head_stride, body, body_bytes, body_off, body_len, out, outlen, out_stride, status, 0}});
     });
 }
 // Compress_d / Decompress_d for any d in 1..12 (ml_kem.c:83-119; d = 12 is the identity there) over n values

@@ -20,6 +20,7 @@
 #include "mlkem_wkeccak.hpp"
 #include "mlkem_small.hpp"
 #include "mlkem_sha3r.hpp"
+#include "mlkem_kmac.hpp"
 #include "mlkem_check.hpp"
 #include <stdlib.h>
 #ifndef MLKEM_EMU
@@ -821,6 +822,59 @@ inline int sha3_ragged_launch(stream_t st, unsigned rate, const Sha3rArgs& a, si
     case 144: launch("k_sha3_ragged", k_sha3_ragged<144>, grid, WAVE, st, a); break;
     case 168: launch("k_sha3_ragged", k_sha3_ragged<168>, grid, WAVE, st, a); break;
     default: return -1;
+    }
+    return 0;
+}
+
+// cSHAKE / KMAC over messages of unequal length (mlkem_kmac.hpp): the call-uniform prefix once (k_kmac_prefix, into the context's
+// midstate region `mid`), then one sponge per wavefront for calls of at most `wave_max` messages -- the ragged SHA-3 call's own
+// limit: the crossover of these kernels is assumed to be that of k_sha3_ragged, not measured -- and one per lane above.  With a shared
+// key the midstate is zeroed in stream order behind the last kernel.  `c` has passed kmac_check_args (rate from there), n > 0.
+inline int kmac_launch(stream_t st, unsigned rate, const KmacCall& c, uint64_t* mid, size_t wave_max) {
+    if (!mid || (rate != 168 && rate != 136)) return -1;
+    KmacArgs a;
+    a.s = c.s;
+    a.s.suffix = 0;
+    const bool per_item = c.kmac && c.key_stride;
+    const bool shared = c.kmac && !c.key_stride;
+    a.key = per_item ? c.key : nullptr;
+    a.key_len = per_item ? c.key_len : 0;
+    a.key_stride = per_item ? c.key_stride : 0;
+    unsigned hl = 0;
+    const uint64_t khdr = c.kmac ? kmac_key_header(rate, c.key_len, hl) : 0;
+    a.khdr = per_item ? khdr : 0;
+    a.khdr_len = per_item ? hl : 4;
+    a.lead = c.lead_len ? kmac_le64(c.lead, c.lead_len) : 0;
+    a.lead_len = c.lead_len;
+    // the tail: right_encode(L) || 04 (KMAC; L = 0 for the XOF variants), 04 (cSHAKE), 1F (N = S = "": SHAKE, no prefix block)
+    uint8_t tb[8] = {0};
+    unsigned tl = 0;
+    const bool plain = !c.kmac && !c.fname_len && !c.custom_len;
+    if (c.kmac) tl = kmac_right_encode(c.xof ? 0ull : 8ull * c.s.outlen, tb);
+    tb[tl++] = plain ? 0x1F : 0x04;
+    a.tail = kmac_le64(tb, tl);
+    a.tail_len = tl;
+    a.mid = plain ? nullptr : mid;
+    if (!plain) {
+        KmacPrefix pre;
+        static const uint8_t kmac_name[4] = {'K', 'M', 'A', 'C'};
+        kmac_build_prefix(pre, rate, c.kmac ? kmac_name : c.fname, c.kmac ? 4u : c.fname_len, c.custom, c.custom_len);
+        launch("k_kmac_prefix", k_kmac_prefix, 1, WAVE, st, pre, rate, shared ? c.key : nullptr, shared ? c.key_len : 0u, shared ? 1 : 0,
+               shared ? khdr : 0ull, shared ? hl : 0u, mid);
+    }
+    if (a.s.n <= wave_max) {
+        launch("k_kmac_ragged", k_kmac_ragged_w, a.s.n, WAVE, st, a, rate);
+    } else {
+        const size_t grid = ceil_div(a.s.n, WAVE);
+        if (rate == 168) launch("k_kmac_ragged", k_kmac_ragged<168>, grid, WAVE, st, a);
+        else launch("k_kmac_ragged", k_kmac_ragged<136>, grid, WAVE, st, a);
+    }
+    if (shared) {   // key-equivalent: gone before anything queued later can read it
+#ifdef MLKEM_EMU
+        memset(mid, 0, KMAC_MID_BYTES);
+#else
+        if (hipMemsetAsync(mid, 0, KMAC_MID_BYTES, st) != hipSuccess) return -1;
+#endif
     }
     return 0;
 }

@@ -318,6 +318,38 @@ MLKEM_API int mlkem_sha3_ragged_dev(mlkem_ctx* ctx, int alg, size_t n, const uin
                                     const uint8_t* body, size_t body_bytes, const uint64_t* body_off, const uint32_t* body_len,
                                     uint8_t* out, unsigned outlen, size_t out_stride, int32_t* status, void* stream);
 MLKEM_API size_t mlkem_sha3_ragged_wide_max(const mlkem_ctx* ctx);
+/* ---- SP 800-185 cSHAKE / KMAC over device-resident messages of unequal length, keyed by device rows in place -------------------
+ * The approved keyed constructions on Keccak, for the KDF or MAC a protocol applies to a shared secret (SP 800-56C, SP 800-108):
+ *   mlkem_cshake_dev  out[i] = cSHAKE<bits>(X_i, 8 * outlen, N = fname, S = custom); fname = custom = "" is SHAKE<bits>
+ *   mlkem_kmac_dev    out[i] = KMAC<bits>(K_i, X_i, 8 * outlen, S = custom), or KMACXOF<bits> (right_encode(0))
+ *   X_i = lead || head[i] || body_i.  lead: 0..8 bytes given on the HOST, the same for every item (e.g. the counter 00 00 00 01
+ *   of the SP 800-56C one-step KDF in front of the shared secret).  head, body, body_off, body_len, out, status: exactly the
+ *   arguments, alignment rules, bounds rule (zero row and status MLKEM_ERR_ARG for an item outside body_bytes or with
+ *   lead_len + head_len + body_len[i] >= 2^31) and memory rule of mlkem_sha3_ragged_dev.
+ * bits: 128 | 256.  alg: MLKEM_KMAC128 .. MLKEM_KMACXOF256.  outlen: 1 .. 65536.
+ * fname (<= 32 bytes) and custom (<= 256 bytes) are HOST pointers to public bytes, read during the call.
+ * key, per item (key_stride >= key_len > 0): device rows used in place, base and key_stride 8-byte aligned, key_len % 8 == 0 and
+ *   8 .. 128 (typically the K rows of the Encaps / Decaps call before, key_stride 32).
+ * key, shared (key_stride == 0): ONE device key of any length 0 .. 512 at any address for all items (e.g. the 164 / 132-byte
+ *   default salt of SP 800-56C).
+ * The call-uniform prefix (the N / S block and a shared key's blocks) is absorbed once per call by a one-wavefront kernel into a
+ * 200-byte midstate region the CONTEXT owns, allocated with the context: no call allocates, every call is a pure function of its
+ * inputs and may be captured from the first one on.  After a shared-key call the region is zeroed in stream order.  The region
+ * serves one call at a time: calls on one context are made on one stream, or ordered by the caller.
+ * The form switch is mlkem_sha3_ragged_dev's (MLKEM_SHA3_WIDE_ITEMS).  Control flow and addresses depend on lengths and offsets
+ * only: key, head and body may be secrets.  n == 0 is a no-op; a bad argument returns MLKEM_ERR_ARG and launches nothing. */
+#define MLKEM_KMAC128 0
+#define MLKEM_KMAC256 1
+#define MLKEM_KMACXOF128 2
+#define MLKEM_KMACXOF256 3
+MLKEM_API int mlkem_cshake_dev(mlkem_ctx* ctx, int bits, size_t n, const uint8_t* fname, unsigned fname_len, const uint8_t* custom,
+                               unsigned custom_len, const uint8_t* lead, unsigned lead_len, const uint8_t* head, unsigned head_len,
+                               size_t head_stride, const uint8_t* body, size_t body_bytes, const uint64_t* body_off,
+                               const uint32_t* body_len, uint8_t* out, unsigned outlen, size_t out_stride, int32_t* status, void* stream);
+MLKEM_API int mlkem_kmac_dev(mlkem_ctx* ctx, int alg, size_t n, const uint8_t* key, unsigned key_len, size_t key_stride,
+                             const uint8_t* custom, unsigned custom_len, const uint8_t* lead, unsigned lead_len, const uint8_t* head,
+                             unsigned head_len, size_t head_stride, const uint8_t* body, size_t body_bytes, const uint64_t* body_off,
+                             const uint32_t* body_len, uint8_t* out, unsigned outlen, size_t out_stride, int32_t* status, void* stream);
 /* host helper, no device work: message bits (one per byte) + suffix ("01" hash / "1111" XOF: sha3.c:408-436) + pad10*1
  * (sha3.c:226-240) -> whole rate blocks in `padded`; returns the number of blocks or a negative error */
 MLKEM_API int mlkem_sha3_pad_bits(const uint8_t* msg_bits, size_t nbits, int xof, unsigned rate, uint8_t* padded, size_t padded_cap);
@@ -360,6 +392,16 @@ MLKEM_API int mlkem_keccak_sponge(unsigned rate, size_t n, const uint8_t* padded
 MLKEM_API int mlkem_sha3_ragged(int alg, size_t n, const uint8_t* head, unsigned head_len, size_t head_stride, const uint8_t* body,
                                 size_t body_bytes, const uint64_t* body_off, const uint32_t* body_len, uint8_t* out, unsigned outlen,
                                 size_t out_stride, int32_t* status);
+/* mlkem_cshake_dev / mlkem_kmac_dev over host pointers: stage, run, synchronise, as mlkem_sha3_ragged.  Every array (the key
+ * included) is a host array and no pointer needs any alignment; a per-item key still has key_len % 8 == 0, 8 .. 128. */
+MLKEM_API int mlkem_cshake(int bits, size_t n, const uint8_t* fname, unsigned fname_len, const uint8_t* custom, unsigned custom_len,
+                           const uint8_t* lead, unsigned lead_len, const uint8_t* head, unsigned head_len, size_t head_stride,
+                           const uint8_t* body, size_t body_bytes, const uint64_t* body_off, const uint32_t* body_len, uint8_t* out,
+                           unsigned outlen, size_t out_stride, int32_t* status);
+MLKEM_API int mlkem_kmac(int alg, size_t n, const uint8_t* key, unsigned key_len, size_t key_stride, const uint8_t* custom,
+                         unsigned custom_len, const uint8_t* lead, unsigned lead_len, const uint8_t* head, unsigned head_len,
+                         size_t head_stride, const uint8_t* body, size_t body_bytes, const uint64_t* body_off, const uint32_t* body_len,
+                         uint8_t* out, unsigned outlen, size_t out_stride, int32_t* status);
 /* Compress / Decompress (ml_kem.c:83-119) over n host values, any d in 1..12 (reference test Test_Archive/CompressDecompress_test04.c) */
 MLKEM_API int mlkem_compress(int d, size_t n, const uint16_t* x, uint16_t* y);
 MLKEM_API int mlkem_decompress(int d, size_t n, const uint16_t* y, uint16_t* x);
