@@ -24,6 +24,9 @@ ERR_RNG = -2                # MLKEM_ERR_RNG: the OS entropy source failed
 ERR_MODULUS = -4            # per-item status of encaps in "fips203" conformance: an ek coefficient >= q
 ERR_HASH = -5
 ERR_KEY = -6                # MLKEM_ERR_KEY: a key failed validation, no key set was created (MLKEMError.key_status says which)
+ERR_LOW_ORDER = -7          # MLKEM_ERR_LOW_ORDER: per-item status of MLKEM.x25519, the output is all zero
+# X-Wing (ML-KEM-768 + X25519): bytes of sk, pk, ct, ss and of the encapsulation seed (include/mlkem_batch.h)
+XWING_SIZES = {"sk": 32, "pk": 1216, "ct": 1120, "ss": 32, "eseed": 64}
 ERR_ARG = -101              # MLKEM_ERR_ARG; also the per-item status of a key-set call whose key index is out of range
 # per-item result bits of MLKEM.check_keys / mlkem_check_keys[_dev] (include/mlkem_batch.h); 0 = every requested check passed
 KEYCHECK_EK_MODULUS = 1     # ek: a ByteDecode_12 coefficient >= q (FIPS 203 §7.2)
@@ -59,6 +62,8 @@ ABI_SYMBOLS = (
     "mlkem_ctx_rng_seed", "mlkem_keygen_random_dev", "mlkem_encaps_random_dev", "mlkem_encaps_keyset_random_dev",
     "mlkem_sha3_ragged_dev", "mlkem_sha3_ragged", "mlkem_sha3_ragged_wide_max",
     "mlkem_cshake_dev", "mlkem_kmac_dev", "mlkem_cshake", "mlkem_kmac",
+    "mlkem_x25519_dev", "mlkem_xwing_keygen_dev", "mlkem_xwing_encaps_dev", "mlkem_xwing_decaps_dev",
+    "mlkem_xwing_keygen_random_dev", "mlkem_xwing_encaps_random_dev",
 )
 # MLKEM.sha3 / mlkem_sha3_ragged[_dev]: name -> (alg code MLKEM_SHA3_224 .. MLKEM_SHAKE256, rate in bytes, digest bytes; 0 = any outlen)
 SHA3_ALGS = {"sha3_224": (0, 144, 28), "sha3_256": (1, 136, 32), "sha3_384": (2, 104, 48), "sha3_512": (3, 72, 64),
@@ -134,6 +139,12 @@ def load_library():
     L.mlkem_keygen_random_dev.argtypes = [vp, i32, sz, vp, vp, vp, vp]
     L.mlkem_encaps_random_dev.argtypes = [vp, i32, sz, vp, vp, vp, vp, vp]
     L.mlkem_encaps_keyset_random_dev.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
+    L.mlkem_x25519_dev.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+    L.mlkem_xwing_keygen_dev.argtypes = [vp, sz, vp, vp, vp]
+    L.mlkem_xwing_encaps_dev.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp]
+    L.mlkem_xwing_decaps_dev.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+    L.mlkem_xwing_keygen_random_dev.argtypes = [vp, sz, vp, vp, vp]
+    L.mlkem_xwing_encaps_random_dev.argtypes = [vp, sz, vp, vp, vp, vp, vp]
     L.mlkem_encaps_status_dev.argtypes = [vp, i32, sz, vp, vp, vp, vp, vp, vp]
     L.mlkem_ctx_set_conformance.argtypes = [vp, i32]
     L.mlkem_ctx_debug_stages.argtypes = [vp, C.c_uint]
@@ -451,6 +462,85 @@ class MLKEM:
         self._check(self.lib.mlkem_encaps_random_dev(self._ctx, self.param_set, n, ek.data_ptr(), c.data_ptr(), K.data_ptr(),
                                                      None if st is None else st.data_ptr(), self._stream()))
         return (c, K, st) if return_status else (c, K)
+
+    # -- batched X25519 and the X-Wing hybrid KEM (mlkem_x25519.hpp, mlkem_xwing.hpp) ----------------
+    def _rows(self, t, last, what):
+        """An input of secret or wire rows: as _dev, but a tensor of another dtype or on another device is refused instead of being
+        converted or copied (a silent host copy of a secret is what these calls exist to avoid)."""
+        torch = self.torch
+        if isinstance(t, torch.Tensor) and (t.dtype != torch.uint8 or t.device != self.device):
+            raise MLKEMError(ERR_ARG, f"{what} must be a uint8 tensor on {self.device}, got {t.dtype} on {t.device}")
+        return self._dev(t, torch.uint8, last)
+
+    def x25519(self, scalar, u=None, return_status=False):
+        """X25519 (RFC 7748 section 5): scalar [n,32], u [n,32] or None (the base point u = 9) -> out [n,32], canonical
+        (+ status [n] int32 with return_status: ERR_LOW_ORDER where the output is all zero).  Constant time, one item per lane."""
+        scalar = self._rows(scalar, 32, "scalar")
+        n = scalar.shape[0]
+        if u is not None:
+            u = self._rows(u, 32, "u")
+            if u.shape[0] != n:
+                raise MLKEMError(ERR_ARG, "scalar and u batch sizes differ")
+        out = self._out(n, 32)
+        st = self.torch.empty(n, dtype=self.torch.int32, device=self.device) if return_status else None
+        self._check(self.lib.mlkem_x25519_dev(self._ctx, n, scalar.data_ptr(), None if u is None else u.data_ptr(), out.data_ptr(),
+                                              None if st is None else st.data_ptr(), self._stream()))
+        return (out, st) if return_status else out
+
+    def xwing_keygen(self, sk):
+        """X-Wing.KeyGen: sk [n,32] -> pk [n,1216] = pk_M || pk_X.  Works on an engine of any param_set (X-Wing fixes ML-KEM-768 in
+        FIPS 203 mode, whatever the engine's conformance)."""
+        sk = self._rows(sk, 32, "sk")
+        n = sk.shape[0]
+        pk = self._out(n, 1216)
+        self._check(self.lib.mlkem_xwing_keygen_dev(self._ctx, n, sk.data_ptr(), pk.data_ptr(), self._stream()))
+        return pk
+
+    def xwing_encaps(self, pk, eseed, return_status=False):
+        """X-Wing.Encaps: pk [n,1216], eseed [n,64] -> ct [n,1120], ss [n,32] (+ status [n] int32 with return_status: ERR_MODULUS
+        where pk_M fails the FIPS 203 modulus check; that item's ct and ss are to be discarded)."""
+        pk, eseed = self._rows(pk, 1216, "pk"), self._rows(eseed, 64, "eseed")
+        n = pk.shape[0]
+        if eseed.shape[0] != n:
+            raise MLKEMError(ERR_ARG, "pk and eseed batch sizes differ")
+        ct, ss = self._out(n, 1120), self._out(n, 32)
+        st = self.torch.empty(n, dtype=self.torch.int32, device=self.device) if return_status else None
+        self._check(self.lib.mlkem_xwing_encaps_dev(self._ctx, n, pk.data_ptr(), eseed.data_ptr(), ct.data_ptr(), ss.data_ptr(),
+                                                    None if st is None else st.data_ptr(), self._stream()))
+        return (ct, ss, st) if return_status else (ct, ss)
+
+    def xwing_decaps(self, sk, ct, pk=None):
+        """X-Wing.Decaps: sk [n,32], ct [n,1120] -> ss [n,32].  pk [n,1216] (optional) saves the second curve multiplication: pk_X is
+        read from its last 32 bytes instead of being recomputed.  A pk that does not belong to sk gives a wrong secret silently."""
+        sk, ct = self._rows(sk, 32, "sk"), self._rows(ct, 1120, "ct")
+        n = sk.shape[0]
+        if pk is not None:
+            pk = self._rows(pk, 1216, "pk")
+        if ct.shape[0] != n or (pk is not None and pk.shape[0] != n):
+            raise MLKEMError(ERR_ARG, "sk, ct and pk batch sizes differ")
+        ss = self._out(n, 32)
+        self._check(self.lib.mlkem_xwing_decaps_dev(self._ctx, n, sk.data_ptr(), ct.data_ptr(), None if pk is None else pk.data_ptr(),
+                                                    ss.data_ptr(), self._stream()))
+        return ss
+
+    def xwing_keygen_random(self, n):
+        """X-Wing.KeyGen for n fresh keys: sk of item i = SHAKE256(root || 0x03 || LE64(pos + i))[:32], derived on the device
+        -> (sk [n,32], pk [n,1216]).  Shares the position counter of keygen_random / encaps_random.  Not capturable."""
+        n = int(n)
+        sk, pk = self._out(n, 32), self._out(n, 1216)
+        self._check(self.lib.mlkem_xwing_keygen_random_dev(self._ctx, n, sk.data_ptr(), pk.data_ptr(), self._stream()))
+        return sk, pk
+
+    def xwing_encaps_random(self, pk, return_status=False):
+        """X-Wing.Encaps with eseed of item i = SHAKE256(root || 0x04 || LE64(pos + i))[:64], derived on the device:
+        pk [n,1216] -> ct [n,1120], ss [n,32] (+ status as xwing_encaps).  Not capturable."""
+        pk = self._rows(pk, 1216, "pk")
+        n = pk.shape[0]
+        ct, ss = self._out(n, 1120), self._out(n, 32)
+        st = self.torch.empty(n, dtype=self.torch.int32, device=self.device) if return_status else None
+        self._check(self.lib.mlkem_xwing_encaps_random_dev(self._ctx, n, pk.data_ptr(), ct.data_ptr(), ss.data_ptr(),
+                                                           None if st is None else st.data_ptr(), self._stream()))
+        return (ct, ss, st) if return_status else (ct, ss)
 
     # reference-style aliases
     KeyGen_internal = keygen

@@ -6,6 +6,7 @@
 #include "mlkem_pipeline.hpp"
 #include "mlkem_keyset.hpp"
 #include "mlkem_rng.hpp"
+#include "mlkem_xwing.hpp"
 #include "mlkem_selftest.hpp"
 
 #include "../../include/mlkem_batch.h"
@@ -88,6 +89,11 @@ struct mlkem_ctx {
     // Allocated with the context, so that no call allocates (a first call may already be captured); zeroed after every shared-key
     // call and before it is freed.
     uint64_t* kmac_mid = nullptr;
+    // staging of the X-Wing calls (mlkem_xwing.hpp: XwingStage rows for min(chunk_items, XWING_SLICE_MAX) items).  Allocated with the
+    // first X-Wing call, as seed_stage is; what a call used of it is zeroed in stream order before the call returns, and the whole
+    // region before it is freed.  The ML-KEM legs of KeyGen and of Decaps above small_max also stage through seed_stage.
+    uint8_t* xwing_stage = nullptr;
+    size_t xwing_items = 0;
 };
 
 // A prepared key set (mlkem_keyset.hpp): ONE device allocation holding the keys | H(ek) | A-hat^T tables, read-only after
@@ -168,6 +174,7 @@ const char* mlkem_strerror(int code) {
     case MLKEM_ERR_MODULUS: return "modulus check failed (reference ml_errno -4; unreachable)";
     case MLKEM_ERR_HASH: return "decapsulation key hash check failed (reference ml_errno -5)";
     case MLKEM_ERR_KEY: return "a key failed validation: no key set was created (see key_status)";
+    case MLKEM_ERR_LOW_ORDER: return "X25519 output is all zero: the peer's u-coordinate is a low-order point";
     case MLKEM_ERR_NO_DEVICE: return "no usable HIP device / HIP runtime error (no CPU fallback exists)";
     case MLKEM_ERR_ARG: return "bad argument (NULL or misaligned pointer)";
     case MLKEM_ERR_ALLOC: return "allocation failed";
@@ -295,6 +302,10 @@ void mlkem_ctx_destroy(mlkem_ctx* ctx) {
     if (ctx->rng_root) {
         (void)hipMemset(ctx->rng_root, 0, 32);
         (void)hipFree(ctx->rng_root);
+    }
+    if (ctx->xwing_stage) {
+        (void)hipMemset(ctx->xwing_stage, 0, ctx->xwing_items * XWING_STAGE_ITEM_BYTES);   // d, z, sk_X, m, ss_M, ss_X of the last slice
+        (void)hipFree(ctx->xwing_stage);
     }
     if (ctx->kmac_mid) {
         (void)hipMemset(ctx->kmac_mid, 0, KMAC_MID_BYTES);
@@ -1754,7 +1765,7 @@ int mlkem_ctx_rng_seed(mlkem_ctx* ctx, const uint8_t* seed) {
 
 // what every random call does once its arguments are accepted and n > 0: refuse a capturing stream (a replay would repeat the
 // positions, and so the keys), seed a context that never was from the OS, and give it its derived-seed region
-static int rng_prepare(mlkem_ctx* ctx, hipStream_t st, size_t n, RngCall& g) {
+static int rng_begin(mlkem_ctx* ctx, hipStream_t st) {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
         (void)hipGetLastError();
@@ -1764,6 +1775,10 @@ static int rng_prepare(mlkem_ctx* ctx, hipStream_t st, size_t n, RngCall& g) {
         const int rc = mlkem_ctx_rng_seed(ctx, nullptr);
         if (rc) return rc;
     }
+    return MLKEM_OK;
+}
+static int rng_prepare(mlkem_ctx* ctx, hipStream_t st, size_t n, RngCall& g) {
+    if (int rc = rng_begin(ctx, st)) return rc;
     if (!ctx->rng_seeds && !hip_ok(hipMalloc(&ctx->rng_seeds, ctx->ws.cap * 64), "hipMalloc(rng seeds)")) {
         ctx->rng_seeds = nullptr;
         return MLKEM_ERR_ALLOC;
@@ -1833,6 +1848,121 @@ int mlkem_encaps_keyset_random_dev(mlkem_ctx* ctx, const mlkem_keyset* ks, size_
     if (int rc = rng_prepare(ctx, st, n, g)) return rc;
     ctx->rng_pos += n;
     const int bad = encaps_keyset_random_run(st, ks->p, ks->v, n, g, key_index, c, K, status, ctx->ws, ctx->ks_lim);
+    HIP_TRY(hipGetLastError());
+    return bad ? MLKEM_ERR_NO_DEVICE : MLKEM_OK;
+}
+
+// ---- batched X25519 and the X-Wing hybrid KEM (mlkem_x25519.hpp, mlkem_xwing.hpp) -------------------------------------------------
+int mlkem_x25519_dev(mlkem_ctx* ctx, size_t n, const uint8_t* scalar, const uint8_t* u, uint8_t* out, int32_t* status, void* stream) {
+    if (n && (!scalar || !out)) return MLKEM_ERR_ARG;
+    if (!aligned16(scalar) || !aligned16(u) || !aligned16(out) || (reinterpret_cast<uintptr_t>(status) & 3u)) return MLKEM_ERR_ARG;
+    if (int rc = rng_ctx_check(ctx)) return rc;
+    if (n == 0) return MLKEM_OK;
+    x25519_launch(static_cast<hipStream_t>(stream), n, scalar, 32, u, 32, out, 32, status);
+    HIP_TRY(hipGetLastError());
+    return MLKEM_OK;
+}
+
+// what every X-Wing call does once its arguments are accepted and n > 0: give the context its staging regions (the first call
+// allocates) and build the call's view of them and its workspace -- the context's, in FIPS 203 mode whatever the context's mode
+// is, and on the caller's stream alone (the overlap of the side stream is not worth a fork beside a 255-step ladder: assumed, not measured)
+static int xwing_prepare(mlkem_ctx* ctx, size_t n, bool need_seed_stage, XwingStage& g, Workspace& ws) {
+    if (!ctx->xwing_stage) {
+        size_t items = std::min(ctx->ws.cap, XWING_SLICE_MAX);
+        if (const char* e = getenv("MLKEM_XWING_SLICE_ITEMS")) {   // measurement aid (tools/xwing_bench.py --slices): at most chunk_items
+            long long v = atoll(e);
+            if (v > 0) items = std::min(ctx->ws.cap, (size_t)v);
+        }
+        if (!hip_ok(hipMalloc(&ctx->xwing_stage, items * XWING_STAGE_ITEM_BYTES), "hipMalloc(xwing staging)")) {
+            ctx->xwing_stage = nullptr;
+            return MLKEM_ERR_ALLOC;
+        }
+        ctx->xwing_items = items;
+    }
+    if (need_seed_stage && !ctx_seed_stage(ctx)) return MLKEM_ERR_ALLOC;   // >= chunk_items x 4800 bytes: a slice of ML-KEM-768 rows fits
+    g.base = ctx->xwing_stage;
+    g.items = std::min(n, ctx->xwing_items);
+    g.dk_stage = ctx->seed_stage;
+    ws = ctx->ws;
+    ws.fips = 1;
+    ws.side_on = false;
+    return MLKEM_OK;
+}
+
+int mlkem_xwing_keygen_dev(mlkem_ctx* ctx, size_t n, const uint8_t* sk, uint8_t* pk, void* stream) {
+    if (n && (!sk || !pk)) return MLKEM_ERR_ARG;
+    if (!aligned16(sk) || !aligned16(pk)) return MLKEM_ERR_ARG;
+    if (int rc = rng_ctx_check(ctx)) return rc;
+    if (n == 0) return MLKEM_OK;
+    XwingStage g;
+    Workspace ws;
+    if (int rc = xwing_prepare(ctx, n, true, g, ws)) return rc;
+    const int bad = xwing_keygen_run(static_cast<hipStream_t>(stream), n, g, sk, pk, ws);
+    HIP_TRY(hipGetLastError());
+    return bad ? MLKEM_ERR_NO_DEVICE : MLKEM_OK;
+}
+
+int mlkem_xwing_encaps_dev(mlkem_ctx* ctx, size_t n, const uint8_t* pk, const uint8_t* eseed, uint8_t* ct, uint8_t* ss, int32_t* status,
+                           void* stream) {
+    if (n && (!pk || !eseed || !ct || !ss)) return MLKEM_ERR_ARG;
+    if (!aligned16(pk) || !aligned16(eseed) || !aligned16(ct) || !aligned16(ss) || (reinterpret_cast<uintptr_t>(status) & 3u)) return MLKEM_ERR_ARG;
+    if (int rc = rng_ctx_check(ctx)) return rc;
+    if (n == 0) return MLKEM_OK;
+    XwingStage g;
+    Workspace ws;
+    if (int rc = xwing_prepare(ctx, n, false, g, ws)) return rc;
+    const int bad = xwing_encaps_run(static_cast<hipStream_t>(stream), n, g, pk, eseed, nullptr, ct, ss, status, ws);
+    HIP_TRY(hipGetLastError());
+    return bad ? MLKEM_ERR_NO_DEVICE : MLKEM_OK;
+}
+
+int mlkem_xwing_decaps_dev(mlkem_ctx* ctx, size_t n, const uint8_t* sk, const uint8_t* ct, const uint8_t* pk, uint8_t* ss, void* stream) {
+    if (n && (!sk || !ct || !ss)) return MLKEM_ERR_ARG;
+    if (!aligned16(sk) || !aligned16(ct) || !aligned16(pk) || !aligned16(ss)) return MLKEM_ERR_ARG;
+    if (int rc = rng_ctx_check(ctx)) return rc;
+    if (n == 0) return MLKEM_OK;
+    XwingStage g;
+    Workspace ws;
+    if (int rc = xwing_prepare(ctx, n, n > ctx->ws.small_max(3), g, ws)) return rc;
+    const int bad = xwing_decaps_run(static_cast<hipStream_t>(stream), n, g, sk, ct, pk, ss, ws);
+    HIP_TRY(hipGetLastError());
+    return bad ? MLKEM_ERR_NO_DEVICE : MLKEM_OK;
+}
+
+int mlkem_xwing_keygen_random_dev(mlkem_ctx* ctx, size_t n, uint8_t* sk_out, uint8_t* pk, void* stream) {
+    if (n && (!sk_out || !pk)) return MLKEM_ERR_ARG;
+    if (!aligned16(sk_out) || !aligned16(pk)) return MLKEM_ERR_ARG;
+    if (int rc = rng_ctx_check(ctx)) return rc;
+    if (n == 0) return MLKEM_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = rng_begin(ctx, st)) return rc;
+    XwingStage g;
+    Workspace ws;
+    if (int rc = xwing_prepare(ctx, n, true, g, ws)) return rc;
+    // sk is the caller's output: derived straight into it (domain 0x03), then the seeded KeyGen reads it
+    xwing_derive_launch(st, false, n, ctx->rng_root, ctx->rng_pos, sk_out, nullptr, ctx->rng_wide_max);
+    ctx->rng_pos += n;
+    const int bad = xwing_keygen_run(st, n, g, sk_out, pk, ws);
+    HIP_TRY(hipGetLastError());
+    return bad ? MLKEM_ERR_NO_DEVICE : MLKEM_OK;
+}
+
+int mlkem_xwing_encaps_random_dev(mlkem_ctx* ctx, size_t n, const uint8_t* pk, uint8_t* ct, uint8_t* ss, int32_t* status, void* stream) {
+    if (n && (!pk || !ct || !ss)) return MLKEM_ERR_ARG;
+    if (!aligned16(pk) || !aligned16(ct) || !aligned16(ss) || (reinterpret_cast<uintptr_t>(status) & 3u)) return MLKEM_ERR_ARG;
+    if (int rc = rng_ctx_check(ctx)) return rc;
+    if (n == 0) return MLKEM_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = rng_begin(ctx, st)) return rc;
+    XwingStage g;
+    Workspace ws;
+    if (int rc = xwing_prepare(ctx, n, false, g, ws)) return rc;
+    RngCall r;
+    r.root = ctx->rng_root;
+    r.pos = ctx->rng_pos;
+    r.wide_max = ctx->rng_wide_max;
+    ctx->rng_pos += n;
+    const int bad = xwing_encaps_run(st, n, g, pk, nullptr, &r, ct, ss, status, ws);
     HIP_TRY(hipGetLastError());
     return bad ? MLKEM_ERR_NO_DEVICE : MLKEM_OK;
 }

@@ -209,6 +209,58 @@ MLKEM_API int mlkem_encaps_random_dev(mlkem_ctx* ctx, int param_set, size_t n, c
 MLKEM_API int mlkem_encaps_keyset_random_dev(mlkem_ctx* ctx, const mlkem_keyset* ks, size_t n, const uint32_t* key_index, uint8_t* c,
                                              uint8_t* K, int32_t* status, void* stream);
 
+/* ---- batched X25519 and the X-Wing hybrid KEM, device pointers -----------------------------------------------------------
+ * X25519 is RFC 7748 section 5: the scalar is clamped, bit 255 of u is ignored, u is taken mod 2^255 - 19 (non-canonical u is
+ * accepted), the output is canonical; u == NULL is the base point u = 9.  One item per SIMD lane, constant time: no branch,
+ * address or loop bound depends on the scalar or on field data, and both live in registers only.
+ *   mlkem_x25519_dev: scalar, u, out : n x 32; status (n int32, or NULL): MLKEM_ERR_LOW_ORDER where out_i is all zero, else 0.
+ *
+ * X-Wing is ML-KEM-768 + X25519 + a SHA3-256 combiner, as stated here (the draft's own test vectors have not been run):
+ *   Label = 5c 2e 2f 2f 5e 5c
+ *   expand(sk[32]):  e = SHAKE256(sk, 96);  d = e[0:32], z = e[32:64], sk_X = e[64:96]
+ *                    (pk_M, dk_M) = ML-KEM-768.KeyGen_internal(d, z);  pk_X = X25519(sk_X, 9)
+ *   KeyGen(sk)            -> pk = pk_M || pk_X                                              (1184 + 32 bytes)
+ *   Encaps(pk, eseed[64]) -> (ct_M, ss_M) = ML-KEM-768.Encaps_internal(pk[0:1184], eseed[0:32]); ek_X = eseed[32:64];
+ *                            ct_X = X25519(ek_X, 9); ss_X = X25519(ek_X, pk[1184:1216]); ct = ct_M || ct_X   (1088 + 32 bytes)
+ *   Decaps(sk, ct)        -> expand(sk); ss_M = ML-KEM-768.Decaps_internal(dk_M, ct[0:1088]); ss_X = X25519(sk_X, ct[1088:1120])
+ *   ss = SHA3-256(ss_M || ss_X || ct_X || pk_X || Label)
+ * ML-KEM here is always FIPS 203 (PRF and J on SHAKE256), whatever the context's conformance mode; the context may have been
+ * created for any parameter set.  There is no all-zero check on ss_X: the combiner binds ct_X and pk_X instead.
+ * Rows are the wire formats: sk n x 32, pk n x 1216, ct n x 1120, ss n x 32, eseed n x 64.  d, z, sk_X, m, ss_M, ss_X and the
+ * expanded dk_M pass through staging regions the context owns -- its own (2560 bytes x min(chunk_items, 2^18) items, allocated
+ * with the first X-Wing call; larger calls are sliced) and, for KeyGen and for Decaps of more than 768 items, the region of
+ * mlkem_decaps_seed_dev -- and what a call used of them is zeroed in stream order before the call returns control of them.
+ * mlkem_ctx_scratch_bytes does not change.  Conventions as above: base pointers 16-byte aligned, n == 0 is a no-op, MLKEM_ERR_ARG
+ * for a NULL or misaligned pointer or a context of another device, MLKEM_ERR_NO_DEVICE for a NULL context without any device;
+ * nothing synchronises.
+ * STREAM CAPTURE: the seeded calls are pure functions of their inputs, but the first call of a context allocates the staging (and
+ * KeyGen / large Decaps the region of mlkem_decaps_seed_dev): capture a call only after an uncaptured call of the same kind and
+ * size class has run on the context.  The X-Wing calls stay on the caller's stream (no fork to the side stream).
+ *
+ * mlkem_xwing_encaps_dev: status (n int32, or NULL): MLKEM_ERR_MODULUS where pk_M fails the FIPS 203 section 7.2 check (ct_i and
+ *   ss_i are still written and must be discarded, as with mlkem_encaps_status_dev), else 0.
+ * mlkem_xwing_decaps_dev: pk (n x 1216, or NULL) saves the second multiplication: pk_X is read from the last 32 bytes of pk_i
+ *   instead of being recomputed from sk_X.  Nothing checks that pk belongs to sk: A WRONG pk GIVES A WRONG SECRET SILENTLY.
+ * The random calls extend the generator above with two domains that share its position counter:
+ *   X-Wing KeyGen item:  sk    = first 32 bytes of block(root, 0x03, pos)   (written to sk_out: it is the caller's private key)
+ *   X-Wing Encaps item:  eseed = first 64 bytes of block(root, 0x04, pos)
+ * They advance the position by n, refuse a capturing stream and seed an unseeded context from the OS, as the random calls above. */
+#define MLKEM_XWING_SK_BYTES 32
+#define MLKEM_XWING_PK_BYTES 1216
+#define MLKEM_XWING_CT_BYTES 1120
+#define MLKEM_XWING_SS_BYTES 32
+#define MLKEM_XWING_ESEED_BYTES 64
+#define MLKEM_ERR_LOW_ORDER (-7)   /* per-item status of mlkem_x25519_dev: the output is all zero */
+MLKEM_API int mlkem_x25519_dev(mlkem_ctx* ctx, size_t n, const uint8_t* scalar, const uint8_t* u, uint8_t* out, int32_t* status, void* stream);
+MLKEM_API int mlkem_xwing_keygen_dev(mlkem_ctx* ctx, size_t n, const uint8_t* sk, uint8_t* pk, void* stream);
+MLKEM_API int mlkem_xwing_encaps_dev(mlkem_ctx* ctx, size_t n, const uint8_t* pk, const uint8_t* eseed, uint8_t* ct, uint8_t* ss,
+                                     int32_t* status, void* stream);
+MLKEM_API int mlkem_xwing_decaps_dev(mlkem_ctx* ctx, size_t n, const uint8_t* sk, const uint8_t* ct, const uint8_t* pk, uint8_t* ss,
+                                     void* stream);
+MLKEM_API int mlkem_xwing_keygen_random_dev(mlkem_ctx* ctx, size_t n, uint8_t* sk_out, uint8_t* pk, void* stream);
+MLKEM_API int mlkem_xwing_encaps_random_dev(mlkem_ctx* ctx, size_t n, const uint8_t* pk, uint8_t* ct, uint8_t* ss, int32_t* status,
+                                            void* stream);
+
 /* ---- shared-key batches, device pointers ---------------------------------------------------------------------------
  * n encapsulations to ONE encapsulation key / n decapsulations under ONE decapsulation key (a server's long-lived key):
  * the same bytes as mlkem_encaps_dev / mlkem_decaps_dev on n replicated keys, but H(ek), the dk hash check and the

@@ -1,8 +1,10 @@
 // tools/valu_ubench2.hip — measurement aid: per-SIMD issue cost (ns and cycles at the measured clock) of single
 // VALU instructions on gfx950, 8 waves per SIMD, 16 independent accumulators, inline asm so the opcode is exact.
+// `valu_ubench2 mul64` runs only the multiply rows (v_mul_lo/hi_u32, the 24-bit forms, v_mad_u64_u32, v_fma_f64) beside v_xor / v_add.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 #define BODY(ASM)                                                                                           \
@@ -86,6 +88,26 @@ KERNEL(k_fmac, "v_fmac_f32 %0, %1, %2")
 KERNEL64(k_pk_fma_f32, "v_pk_fma_f32 %0, %0, %1, %2")
 KERNEL64(k_pk_add_f32, "v_pk_add_f32 %0, %0, %1")
 KERNEL64(k_pk_mul_f32, "v_pk_mul_f32 %0, %0, %1")
+KERNEL64(k_fma_f64, "v_fma_f64 %0, %0, %1, %2")
+// 32 x 32 + 64 -> 64-bit multiply-add (the limb product of a multi-precision field multiplication): 64-bit accumulators, 32-bit factors
+__global__ void __launch_bounds__(256) k_mad_u64_u32(uint32_t* out, int iters) {
+    unsigned long long r[16];
+    uint32_t m[16];
+    _Pragma("unroll") for (int i = 0; i < 16; i++) {
+        m[i] = threadIdx.x * 2654435761u + i * 40503u + blockIdx.x;
+        r[i] = m[i] * 0x100000001ull;
+    }
+    for (int it = 0; it < iters; it++) {
+        _Pragma("unroll") for (int rep = 0; rep < 4; rep++) {
+            _Pragma("unroll") for (int i = 0; i < 16; i++) {
+                asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(r[i]) : "v"(m[(i + 5) & 15]), "v"(m[(i + 9) & 15]) : "vcc");
+            }
+        }
+    }
+    unsigned long long acc = 0;
+    _Pragma("unroll") for (int i = 0; i < 16; i++) acc ^= r[i];
+    out[blockIdx.x * blockDim.x + threadIdx.x] = (uint32_t)(acc ^ (acc >> 32));
+}
 KERNEL(k_fma_sgpr, "v_fma_f32 %0, %0, s4, %1")
 KERNEL(k_add_lit, "v_add_f32 %0, 0x4b400000, %0")
 KERNEL(k_cvt_sdwa, "v_cvt_f32_u32_sdwa %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1")
@@ -119,8 +141,13 @@ double run(const char* name, kfn_t k, double ref_ns) {
     return ns;
 }
 #define RUN(k) run(#k, k, ref)
-int main() {
+int main(int argc, char** argv) {
     double ref = run("k_xor", k_xor, 0);
+    if (argc > 1 && !strcmp(argv[1], "mul64")) {   // the rows a multi-precision multiplication is chosen by (profiles/x25519_valu_ubench.txt)
+        RUN(k_add); RUN(k_mul_lo); RUN(k_mul_hi); RUN(k_mul_u24); RUN(k_mad_u24); RUN(k_mad_u64_u32); RUN(k_fma_f64); RUN(k_fma_f32);
+        ref = run("k_xor(again)", k_xor, 0); RUN(k_mad_u64_u32); RUN(k_fma_f64);
+        return 0;
+    }
     RUN(k_bitop3); RUN(k_alignbit_c); RUN(k_alignbit_v); RUN(k_alignbyte); RUN(k_perm); RUN(k_lshl); RUN(k_lshl_or); RUN(k_and_or);
     RUN(k_or3); RUN(k_bfe_u); RUN(k_bfe_i); RUN(k_lshl_add); RUN(k_add3); RUN(k_add); RUN(k_sub); RUN(k_min); RUN(k_ashr); RUN(k_and);
     RUN(k_mul_u24); RUN(k_mul_i24); RUN(k_mul_hi_u24); RUN(k_mad_u24); RUN(k_mad_i24); RUN(k_mul_lo); RUN(k_mul_hi); RUN(k_mul_hi_i32);
